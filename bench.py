@@ -12,8 +12,19 @@ synthetic N(0, 1) meshes resident in HBM (no checkpoint/dataset egress).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
                        [--topology craniofacial|synth5k]
+                       [--dump-outputs DIR] [--full]
 (for N > 1 launch with torch.distributed.run, one rank per GPU).
 Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times exactly K steps, writes the last timed
+step's outputs when ``--dump-outputs DIR`` is given, and prints the headline
+line (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``,
+``ms_per_step``, the workload's ``config``).  ``--full`` adds every secondary
+measurement and check to that line: the per-kernel and whole-step rooflines,
+the bf16 block, the synthetic ~5k-vertex line, C1 parity against the golden
+reconstructions, the CPU baseline, and at N > 1 the ranks' self-verification
+(``--no-cpu`` / ``--no-extras`` / ``--no-bf16`` / ``--cpu-seconds`` select
+among those and mean nothing without ``--full``).
 """
 import argparse
 import json
@@ -62,12 +73,18 @@ def parse():
                    help="configuration C5: train on N spectral-interpolation meshes (k = 1000 eigenvectors of "
                         "the template, pairs of the demo meshes) generated on the device and resident in HBM, "
                         "N / world per rank, instead of N(0, 1) meshes")
-    p.add_argument("--cpu-seconds", type=float, default=24.0, help="CPU-baseline sample budget")
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed (reconstruction, "
+                        "latent, losses, gradient, updated parameters) as DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements and checks (rooflines, bf16 block, synthetic ~5k "
+                        "line, C1 parity, CPU baseline, N > 1 self-verification) and add them to the line")
+    p.add_argument("--cpu-seconds", type=float, default=24.0, help="--full: CPU-baseline sample budget")
+    p.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     p.add_argument("--no-extras", action="store_true",
-                   help="skip the secondary measurements (synthetic ~5k line, kernel trace, bf16 block)")
+                   help="--full: skip the secondary measurements (synthetic ~5k line, kernel trace, bf16 block)")
     p.add_argument("--no-bf16", action="store_true",
-                   help="skip the bf16 block (configs C3/C5's precision, timed in the same run)")
+                   help="--full: skip the bf16 block (configs C3/C5's precision, timed in the same run)")
     return p.parse_args()
 
 
@@ -121,7 +138,10 @@ class Runner:
         self.eng = E.SDVAEEngine(self.topo, E.ModelSpec(latent_size=75), lr=1e-4, swap_bs=4,
                                  seed=1234 + rank, device=device, precision=precision,
                                  vertex_major=vertex_major)
-        self.eng.reset_parameters()  # same init on every rank (broadcast below)
+        # same init on every rank (broadcast below), from a seeded generator of
+        # its own: the device's default generator starts from a fresh random
+        # seed in every process, and the inputs must not change from run to run
+        self.eng.reset_parameters(generator=torch.Generator(device=device).manual_seed(1234))
         self.world, self.rank = world, rank
         nv = self.topo.n_verts[0]
         if meshes is None:
@@ -720,6 +740,31 @@ def timed(runner, steps, warmup, world, device):
     return el_rank, cdist.max_over_ranks(el_rank, device)
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # all files of one --dump-outputs together
+
+
+def dump_outputs(runner, out_dir):
+    """``--dump-outputs``: what the last timed step left for its caller, one
+    float32 ``<name>.npy`` each -- the step's reconstruction, latent code and
+    mu / log-variance, its five loss terms, the loss accumulator over all
+    steps so far, the flat gradient, and the parameters and Adam moments
+    after the update.  The data set, the initial weights, the batch order and
+    the noise are all seeded, so two builds run with the same arguments see
+    the same inputs.  An array over its equal share of the 64 MB budget is
+    written as a fixed (seed 0) sorted sample of its flattened elements."""
+    b, P = runner.b, runner.eng.params
+    arrays = {"recon": b.out, "z": b.z, "mulv": b.mulv, "losses": b.losses, "loss_acc": runner.eng.loss_acc,
+              "grad": P.grad, "params": P.data, "exp_avg": P.exp_avg, "exp_avg_sq": P.exp_avg_sq}
+    share = DUMP_BUDGET_BYTES // len(arrays) // 4  # elements per file
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().contiguous().numpy()  # logical [B, V, C] order whatever the device layout
+        if a.size > share:
+            pick = np.sort(np.random.RandomState(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def bf16_block(args, world, rank, device):
     """Configs C3 / C5's precision in the same run: the same step (same
     workload, per-GPU batch and parallelism) with bf16 level-0/1 tensors on
@@ -766,16 +811,48 @@ def main():
                     meshes=meshes, norm=norm, vertex_major=not args.batch_major)
     del meshes
     el_rank, el = timed(runner, args.steps, args.warmup, world, device)
-    dcheck = dist_check(runner, el_rank, args.steps, backend, os.environ.get("CFSD_SHARE_DEVICE")) \
-        if world > 1 else None
     meshes = 16 * world * args.steps
     ms_per_step = el / args.steps * 1e3
+    runner.eng.check_health()  # the one-launch bottleneck backward never gave up waiting
+    if args.dump_outputs and rank == 0:  # before anything below runs another step on these buffers
+        dump_outputs(runner, args.dump_outputs)
+    bf = runner.precision == "bf16"
+    head = {
+        "metric": METRIC, "value": meshes / el, "unit": "meshes/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16" if bf else "fp32",
+        "data": ("spectral-interpolation augmented meshes generated on the device, resident in HBM, "
+                 "random-init weights" if aug_info else
+                 "synthetic N(0,1) meshes resident in HBM, random-init weights"),
+        "augmented_set": aug_info,
+        "config": {"workload": "craniofacial.yaml SD-VAE train step (swap bs 4->16, fwd, "
+                               "MSE+Laplacian+KL+latent-consistency, bwd, Adam)",
+                   "precision": runner.precision,
+                   "layout": "vertex-major levels 0-1" if 0 in runner.b.xl else "batch-major",
+                   "topology": args.topology, "template_vertices": runner.topo.n_verts[0],
+                   "levels": runner.topo.n_verts,
+                   "global_batch": 16 * world, "per_gpu_batch": 16,
+                   "resident_meshes_per_gpu": runner.data.n_items,
+                   "parallelism": f"dp{world}", "graph": runner.use_graph,
+                   "step_graph": ("one graph per step" if runner.ts.one_graph else "three graphs") +
+                                 (", collectives captured" if (world > 1 and runner.ts.one_graph) else ""),
+                   "step_graph_fallback": runner.ts.fallback,
+                   "collective": None if world == 1 else
+                   (("rccl" if backend == "nccl" else backend) + " all_reduce, 2 buckets overlapped")},
+    }
+    if not args.full:  # the plain run ends here: nothing but what the headline figure needs
+        if rank == 0:
+            print(json.dumps(head))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    dcheck = dist_check(runner, el_rank, args.steps, backend, os.environ.get("CFSD_SHARE_DEVICE")) \
+        if world > 1 else None
     losses = runner.eng.loss_acc.cpu().numpy()
     finite = bool(np.isfinite(losses).all())
-    runner.eng.check_health()  # the one-launch bottleneck backward never gave up waiting
     probe = kernel_probe(runner)
     steprf = None if args.no_extras else step_roofline(runner, ms_per_step)
-    bf = runner.precision == "bf16"
     bfb = None
     if not (bf or args.no_extras or args.no_bf16 or args.augmented or args.batch_major):
         bfb = bf16_block(args, world, rank, device)
@@ -792,28 +869,7 @@ def main():
             except (ImportError, AttributeError) as e:  # precompute not available
                 s5k = {"error": str(e)}
         d3, _, roof = d3_roofline(runner, probe, args.topology)
-        out = {
-            "metric": METRIC, "value": meshes / el, "unit": "meshes/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16" if bf else "fp32",
-            "data": ("spectral-interpolation augmented meshes generated on the device, resident in HBM, "
-                     "random-init weights" if aug_info else
-                     "synthetic N(0,1) meshes resident in HBM, random-init weights"),
-            "augmented_set": aug_info,
-            "config": {"workload": "craniofacial.yaml SD-VAE train step (swap bs 4->16, fwd, "
-                                   "MSE+Laplacian+KL+latent-consistency, bwd, Adam)",
-                       "precision": runner.precision,
-                       "layout": "vertex-major levels 0-1" if 0 in runner.b.xl else "batch-major",
-                       "topology": args.topology, "template_vertices": nv, "levels": runner.topo.n_verts,
-                       "global_batch": 16 * world, "per_gpu_batch": 16,
-                       "resident_meshes_per_gpu": runner.data.n_items,
-                       "parallelism": f"dp{world}", "graph": runner.use_graph,
-                       "step_graph": ("one graph per step" if runner.ts.one_graph else "three graphs") +
-                                     (", collectives captured" if (world > 1 and runner.ts.one_graph) else ""),
-                       "step_graph_fallback": runner.ts.fallback,
-                       "collective": None if world == 1 else
-                       (("rccl" if backend == "nccl" else backend) + " all_reduce, 2 buckets overlapped")},
+        out = dict(head, **{
             "roofline": roof,
             "d3_kernels": d3,
             "bf16": bfb,
@@ -828,7 +884,7 @@ def main():
             "parity": parity,
             "cpu_baseline": cpu,
             "losses_mean": (losses[:5] / max(losses[5], 1)).tolist(), "losses_finite": finite,
-        }
+        })
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

@@ -5,7 +5,6 @@ import json
 import os
 
 import numpy as np
-import pytest
 import torch
 
 import cfsd_loader
@@ -43,11 +42,16 @@ def test_obj_reader_and_jsonl(tmp_path):
     assert json.loads(open(w.path).read()) == {"tag": "train/tot", "value": 0.5, "step": 1}
 
 
-def test_refcache_reads_reference_precomputed(topo_npz):
-    ref = "/root/reference/demo_files"
-    if not os.path.exists(os.path.join(ref, "spirals.pkl")):
-        pytest.skip("reference demo_files not present (build container only)")
-    h = refcache.load_precomputed(ref)
+def test_refcache_reads_reference_precomputed(topo_npz, tmp_path):
+    """The reference's own demo cache (``spirals.pkl`` / ``transforms.pkl``,
+    stored xz-compressed under tests/golden/refcache) against the committed
+    topology fixture."""
+    import lzma
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "refcache")
+    for name in ("spirals.pkl", "transforms.pkl"):
+        with lzma.open(os.path.join(src, name + ".xz")) as f:
+            (tmp_path / name).write_bytes(f.read())
+    h = refcache.load_precomputed(str(tmp_path))
     for l in range(4):
         assert np.array_equal(h[f"spiral_{l}"], topo_npz[f"spiral_{l}"])
         for k in ("down", "up"):

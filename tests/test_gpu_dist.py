@@ -241,7 +241,7 @@ def test_bench_line_self_verifies_at_world2(tmp_path):
     env = dict(os.environ, CFSD_DIST_BACKEND="gloo", CFSD_SHARE_DEVICE="1", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "4", "--warmup", "2", "--dataset", "32", "--no-cpu", "--no-extras"]
+           "--gpus", "2", "--steps", "4", "--warmup", "2", "--dataset", "32", "--full", "--no-cpu", "--no-extras"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -11,10 +11,10 @@ for s in ${*:-tests bench prof32}; do
       timeout -k 10 900 python -u -m pytest ${PYTEST_FILES:-tests} -x -v -m gpu --timeout 200 --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"} > $O/tests.log 2>&1 || { grep -E "FAIL|Error" $O/tests.log | head -20; tail -60 $O/tests.log; exit 1; }
       tail -2 $O/tests.log ;;
     bench)
-      timeout -k 10 400 python bench.py ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+      timeout -k 10 400 python bench.py --full ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
       cut -c1-600 $O/bench.json; echo ;;
     bench16)
-      timeout -k 10 300 python bench.py --precision bf16 --no-cpu --steps 2000 ${BENCH_ARGS} > $O/bench_bf16.json 2> $O/bench_bf16.err || { tail -30 $O/bench_bf16.err; exit 1; }
+      timeout -k 10 300 python bench.py --full --precision bf16 --no-cpu --steps 2000 ${BENCH_ARGS} > $O/bench_bf16.json 2> $O/bench_bf16.err || { tail -30 $O/bench_bf16.err; exit 1; }
       cut -c1-600 $O/bench_bf16.json; echo ;;
     prof32|prof16)
       P=fp32; [ $s = prof16 ] && P=bf16
