@@ -23,7 +23,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import bwd_plan, ops
 from .ops import ACT_ELU, ACT_NONE
 
 
@@ -197,16 +197,14 @@ class SDVAEEngine:
         self.fuse_bottleneck = not os.environ.get("CFSD_SHARE_DEVICE")
         # the feature swap and the first Enblock's conv as one launch (cfsd_spiral_conv_fwd_in_swap)
         self.fuse_swap = True
-        # vertex-major levels whose fp32 Deblock backward runs as one dx + dW launch
-        # (cfsd_spiral_conv_bwd_flat_pair): level 1 (D2: 37.8 vs 20.8 + 19.9 us,
-        # step 0.563 vs 0.568 ms same-box); at level 0 the pair is slower (117.5 vs
-        # 51.4 + 52.0 us: the dx role's 12-wave workgroups lose to its 2-per-CU kernel)
+        # The three below are read once per batch size, when buffers() builds the backward plan
+        # (bwd_plan: its kinds carry the measurements); the fuse_* flags above, on every call.
+        # vertex-major levels whose Deblock backward runs as one dx + dW launch
+        # (cfsd_spiral_conv_bwd_flat_pair fp32, ..._flat_pair_bf16 bf16)
         self.vm_pair_levels = {1}
-        # the bf16 step's pair (cfsd_spiral_conv_bwd_flat_pair_bf16) at both vertex-major
-        # levels: D3 29.0 vs 20.0 + 19.0 us, D2 14.7 vs 10.4 + 11.6 us, step 0.427 -> 0.409 ms;
-        # and the bf16 Enblock's dx + dW pair (cfsd_spiral_conv_bwd_rowsub_pair_bf16)
-        self.rowsub_pair16 = True
         self.vm_pair_levels16 = {0, 1}
+        # the bf16 Enblock's dx + dW pair (cfsd_spiral_conv_bwd_rowsub_pair_bf16)
+        self.rowsub_pair16 = True
         n_reg = topo.n_regions if topo.n_regions else 1
         self.region_size = self.spec.latent // n_reg if topo.n_regions else 0
         if topo.n_regions and self.w_lc and self.spec.latent % n_reg:
@@ -434,92 +432,28 @@ class SDVAEEngine:
         b.bn_sync = torch.zeros(ops.BN_SYNC_INTS, dtype=torch.int32, device=dev)  # cfsd_bottleneck_bwd's counters
         b.bn_xchg = (f(ops.bottleneck_exchange_floats(bsz, lat, flat_out, nmulv)) if b.dz_parts is not None
                      else None)  # cfsd_bottleneck_bwd's line-exclusive hand-off area
-        b.dpre_enc = [f(bsz, nv[lv + 1], cout) if (lv == last_enc or not T.enc_select[lv])
+        # grad wrt the Enblock conv's pre-ELU output: at the kept rows, or (Pool(down) no selection) at every row
+        b.dpre_enc = [f(bsz, nv[lv], cout) if not T.enc_select[lv] else f(bsz, nv[lv + 1], cout) if lv == last_enc
                       else fl(lv + 1, bsz, nv[lv + 1], cout) for (cin, cout, lv) in S.enc_layers()]
-        b.g_enc_in = [None] + [f(bsz, nv[lv], cin) if not T.enc_select[lv - 1] else None
-                               for (cin, cout, lv) in S.enc_layers()[1:]]
         b.g_pooled = [f(bsz, nv[lv + 1], cout) if not T.enc_select[lv] else None
                       for (cin, cout, lv) in S.enc_layers()]
-        ws = 0
-        for (cin, cout, lv) in S.enc_layers():
-            rows = nv[lv + 1] if T.enc_select[lv] else nv[lv]
-            ws = max(ws, ops.spiral_conv_bwd_weight_workspace(bsz, rows, T.seq[lv], cin, cout))
-        for (cin, cout, lv, _) in S.dec_layers():
-            ws = max(ws, ops.spiral_conv_bwd_weight_workspace(bsz, nv[lv], T.seq[lv], cin, cout))
-        ws = max(ws, ops.spiral_conv_bwd_weight_workspace(bsz, nv[0], T.seq[0], S.out_ch[0], S.in_ch))
-        for (cin, cout, lv) in S.enc_layers():
-            rows = nv[lv + 1] if T.enc_select[lv] else nv[lv]
-            ws = max(ws, ops.spiral_conv_workspace(bsz, nv[lv], rows, T.seq[lv], cin, cout))
-        for (cin, cout, lv, _) in S.dec_layers():
-            ws = max(ws, ops.spiral_conv_workspace(bsz, nv[lv], nv[lv], T.seq[lv], cin, cout))
-        ws = max(ws, ops.spiral_conv_workspace(bsz, nv[0], nv[0], T.seq[0], S.out_ch[0], S.in_ch))
-        ws = max(ws, ops.spiral_conv_bwd_workspace(bsz, nv[0], nv[0], T.seq[0], S.out_ch[0], S.in_ch))
-        # bf16 Enblocks whose dpre is fp32: dx by the row-subset dG + gather
-        b.rowsub_x = {}
-        for (cin, cout, lv) in S.enc_layers():
-            if lv in lp and lv > 0 and T.enc_select[lv] and T.enc_flat[lv] is not None and lv + 1 not in lp:
-                need = ops.spiral_conv_bwd_data_rowsub_workspace(bsz, nv[lv + 1], T.seq[lv], cin)
-                b.rowsub_x[lv] = need > 0
-                ws = max(ws, need)
+        # every conv layer's backward path (bwd_plan); b.vm_pair: the Deblocks run as one flat-pair launch
+        b.plan = bwd_plan.build(self, b)
+        b.vm_pair = {k: L.kind in (bwd_plan.flat_pair16, bwd_plan.flat_pair32) for k, L in b.plan.items()
+                     if k[0] == "dec"}
+        # shared workspace: the largest forward / dx / dW / row-subset dG need of any conv layer
+        ws = ops.spiral_conv_bwd_workspace(*b.plan["out"].shape)
+        for L in b.plan.values():
+            ws = max(ws, ops.spiral_conv_bwd_weight_workspace(L.bsz, L.rows, L.seq, L.cin, L.cout),
+                     ops.spiral_conv_workspace(*L.shape), L.dg_bytes)
         b.ws = torch.empty(ws // 4 + 64, dtype=torch.float32, device=dev)
-        # weight-gradient partials: one region per layer, all reduced by ONE
-        # cfsd_dw_reduce_batch launch at the end of the backward
-        # (coarse layers whose dx and dW run as one paired launch keep the
-        # paired call's workspace: dW slabs in the same region)
-        regions = [("out", ops.spiral_conv_bwd_workspace(bsz, nv[0], nv[0], T.seq[0], S.out_ch[0],
-                                                         S.in_ch))]
-        b.paired = {}
-
-        b.rowsub = {}
-        b.rowsub_vm = {}
-
-        def dw_region(key, vsrc, rows, seq, cin, cout, has_dx, low, flat=None):
-            b.paired[key] = (not low) and has_dx and ops.spiral_conv_bwd_paired(bsz, vsrc, rows, seq, cin, cout)
-            # Enblock conv on a row subset: dG at the kept rows + flat-list gather
-            rs = ops.spiral_conv_bwd_rowsub_workspace(bsz, vsrc, rows, seq, cin, cout)
-            # fp32 vertex-major input (E1 of the fp32 step): the same paired
-            # dG + dW-slab launch reading x vertex-major (few-row layers)
-            b.rowsub_vm[key] = (low and not self.lp_levels and has_dx and flat is not None and rs > 0
-                                and bsz * rows < 65536)
-            b.rowsub[key] = ((not low) or b.rowsub_vm[key]) and has_dx and flat is not None and rs > 0
-            if b.rowsub[key]:
-                regions.append((key, rs))
-                return
-            if low:
-                nb = ops.spiral_conv_bwd_weight_x_workspace(bsz, rows, seq, cin, cout, ldt if cin > 3 else torch.float32)
-                if b.vm_pair.get(key):
-                    nb = max(nb, ops.spiral_conv_bwd_flat_pair_workspace(bsz, rows, seq, cin, cout))
-            else:
-                nb = (ops.spiral_conv_bwd_workspace(bsz, vsrc, rows, seq, cin, cout) if b.paired[key]
-                      else ops.spiral_conv_bwd_weight_workspace(bsz, rows, seq, cin, cout))
-            regions.append((key, nb))
-
-        # fp32 vertex-major Deblocks (levels in vm_pair_levels): dx + dW slabs in one launch
-        b.vm_pair = {}
-        for i, (cin, cout, lv, _) in enumerate(S.dec_layers()):
-            flat_ok = lv in lp and cin == 32 and cout == 32 and self._flat_dx(b, lv, cin, cout)
-            if ldt == torch.float32:
-                b.vm_pair[("dec", i)] = (flat_ok and lv in self.vm_pair_levels
-                                         and ops.spiral_conv_bwd_flat_pair_workspace(bsz, nv[lv], T.seq[lv], cin,
-                                                                                     cout) > 0)
-            else:
-                b.vm_pair[("dec", i)] = flat_ok and lv in self.vm_pair_levels16
-        for i, (cin, cout, lv, _) in enumerate(S.dec_layers()):
-            dw_region(("dec", i), nv[lv], nv[lv], T.seq[lv], cin, cout, True, lv in lp)
-        for (cin, cout, lv) in S.enc_layers():
-            rows = nv[lv + 1] if T.enc_select[lv] else nv[lv]
-            dw_region(("enc", lv), nv[lv], rows, T.seq[lv], cin, cout, lv > 0, lv in lp,
-                      T.enc_flat[lv] if T.enc_select[lv] else None)
-        total = sum((nb // 4 + 64) // 64 * 64 for _, nb in regions)
-        b.ws_dw_all = torch.empty(total, dtype=torch.float32, device=dev)
-        b.ws_dw, off = {}, 0
-        for key, nb in regions:
-            n = (nb // 4 + 64) // 64 * 64
-            b.ws_dw[key] = b.ws_dw_all[off:off + n]
-            off += n
-        flat_in = self.num_vert * S.out_ch[-1]
-        nmu = lat * (2 if S.is_vae else 1)
-        lws = max(ops.linear_workspace(bsz, flat_in, nmu), ops.linear_workspace(bsz, lat, flat_in))
+        # weight-gradient partials: one region per layer, sized by the layer's
+        # kind (a paired launch keeps its whole workspace there, dW slabs first),
+        # all reduced by ONE cfsd_dw_reduce_batch launch at the end of the backward
+        sizes = {k: (L.nbytes // 4 + 64) // 64 * 64 for k, L in b.plan.items()}
+        b.ws_dw_all = torch.empty(sum(sizes.values()), dtype=torch.float32, device=dev)
+        b.ws_dw = dict(zip(sizes, b.ws_dw_all.split(list(sizes.values()))))
+        lws = max(ops.linear_workspace(bsz, flat_out, nmulv), ops.linear_workspace(bsz, lat, flat_out))
         b.lin_ws = torch.empty(lws // 4 + 64, dtype=torch.float32, device=dev)
         # step bookkeeping for the resident-dataset path
         b.batch_idx = torch.zeros(self.swap_bs, dtype=torch.int32, device=dev)
@@ -715,7 +649,6 @@ class SDVAEEngine:
         ``fuse_adam``: single process, nothing between gradient and update
         (Adam then rides in backward_tail's batched reduce)."""
         T, S, P = self.topo, self.spec, self.params
-        n = S.n
         side_items = []  # deferred weight-gradient slab sets (reduced in one launch later)
         pending, acc = getattr(b, "pending_finalize", (False, None))
         if pending:
@@ -725,62 +658,17 @@ class SDVAEEngine:
             b.pending_finalize = (False, None)
         else:
             ops.recon_lap_bwd(b.out, b.x, b.unit, T.lapT_csr, b.dout, 1.0, self.w_lap)
-        # final SpiralConv (no activation): dpre = dout
-        last_in = b.dec_out[-1]
-        # dX and dW/db of the output conv in one source-row pass.  Every conv
-        # weight gradient is deferred (partials left in b.ws_dw[...]) and all
-        # of them are reduced by one launch at the end.
-        # (weight gradients on a side stream overlapping the dx chain were
-        # measured slower on MI355X, 16.3k vs 17.5k meshes/s: the persistent
-        # level-0 kernels slow ~2x when sharing the chip and every fork/join
-        # costs 6-17 us inside the graph -> one stream)
-        def defer(d, name):
-            side_items.append((d, P.gview(name + ".weight"), P.gview(name + ".bias")))
-
-        weight_grad = ops.spiral_conv_bwd_weight
-
-        w_out = P.view(f"de_layers.{n + 1}.layer.weight")
-        if self._flat_out(b):  # vertex-major: one walk of each vertex's flat inverse list
-            _, d = ops.spiral_conv_bwd_out_flat(last_in, T.spiral[0], b.dout, T.spiral_flat[0], w_out, None, None,
-                                                dx=b.dpre_dec[-1], elu_y=last_in, workspace=b.ws_dw["out"])
-        else:
-            bwd_out = ops.spiral_conv_bwd_x if 0 in b.xl else ops.spiral_conv_bwd
-            _, d = bwd_out(last_in, T.spiral[0], b.dout, T.spiral_inv[0], w_out, None, None,
-                           dx=b.dpre_dec[-1], elu_y=last_in, workspace=b.ws_dw["out"])
-        defer(d, f"de_layers.{n + 1}.layer")
+        # Every conv layer runs the launches its plan record chose (bwd_plan); its weight
+        # gradient is deferred (partials left in b.ws_dw[...]) and one launch reduces them all.
+        # (weight gradients on a side stream overlapping the dx chain were measured slower
+        # on MI355X, 16.3k vs 17.5k meshes/s: the persistent level-0 kernels slow ~2x when
+        # sharing the chip and every fork/join costs 6-17 us inside the graph -> one stream)
+        b.plan["out"].run(self, b, side_items)
         dec = S.dec_layers()
         fused_bn = self._fused_bottleneck_ok(b)
         for i in reversed(range(len(dec))):
-            cin, cout, lv, ui = dec[i]
-            w, _ = self._dec_w(i)
-            if b.vm_pair.get(("dec", i)) and b.dec_up[i].dtype == torch.bfloat16:  # bf16: the same pair
-                defer(ops.spiral_conv_bwd_flat_pair_bf16(b.dec_up[i], T.spiral[lv], b.dpre_dec[i], T.spiral_flat[lv],
-                                                         self._wx(f"de_layers.{i + 1}.conv.layer.weight"),
-                                                         b.g_dec_up[i], workspace=b.ws_dw[("dec", i)]),
-                      f"de_layers.{i + 1}.conv.layer")
-            elif b.vm_pair.get(("dec", i)):  # fp32 vertex-major: flat dx + dW slabs in one launch
-                defer(ops.spiral_conv_bwd_flat_pair(b.dec_up[i], T.spiral[lv], b.dpre_dec[i], T.spiral_flat[lv],
-                                                    w, None, None, b.g_dec_up[i],
-                                                    workspace=b.ws_dw[("dec", i)]), f"de_layers.{i + 1}.conv.layer")
-            elif lv in b.xl:  # vertex-major (bf16 or fp32) operands: dW slabs + dx
-                defer(ops.spiral_conv_bwd_weight_x(b.dec_up[i], T.spiral[lv], b.dpre_dec[i], None, None,
-                                                   b.ws_dw[("dec", i)]), f"de_layers.{i + 1}.conv.layer")
-                w16 = self._wx(f"de_layers.{i + 1}.conv.layer.weight")
-                if self._flat_dx(b, lv, cin, cout):  # vertex-major, batch % 16: one MFMA per list entry
-                    ops.spiral_conv_bwd_data_flat(b.dpre_dec[i], T.spiral_flat[lv], w16, T.n_verts[lv],
-                                                  out=b.g_dec_up[i])
-                else:
-                    ops.spiral_conv_bwd_data_x(b.dpre_dec[i], T.spiral_inv[lv], w16, T.n_verts[lv],
-                                               out=b.g_dec_up[i])
-            elif b.paired[("dec", i)]:  # dx + dW slabs in one launch
-                _, d = ops.spiral_conv_bwd(b.dec_up[i], T.spiral[lv], b.dpre_dec[i], T.spiral_inv[lv],
-                                           w, None, None, dx=b.g_dec_up[i], workspace=b.ws_dw[("dec", i)])
-                defer(d, f"de_layers.{i + 1}.conv.layer")
-            else:
-                defer(weight_grad(b.dec_up[i], T.spiral[lv], b.dpre_dec[i], None, None,
-                                  b.ws_dw[("dec", i)]), f"de_layers.{i + 1}.conv.layer")
-                ops.spiral_conv_bwd_data(b.dpre_dec[i], T.spiral_inv[lv], w, T.n_verts[lv],
-                                         out=b.g_dec_up[i], workspace=b.ws)
+            lv, ui = dec[i][2:]
+            b.plan["dec", i].run(self, b, side_items)
             # a vertex-major source is swept in natural row order, XCD k taking the
             # k-th eighth of the rows (neighbouring rows share source blocks in its L2):
             # 17-19 vs 21.6 us at level 0; batch-major keeps the longest-rows-first order
@@ -866,13 +754,6 @@ class SDVAEEngine:
         for b in self._bufs.values():
             ops.bottleneck_check(b.bn_sync)
 
-    def _flat_out(self, b):
-        """The flat-list output-conv backward applies (vertex-major level 0,
-        batch % 16, the 32 -> 3 xyz conv)."""
-        S = self.spec
-        return (0 in b.xl and b.bsz % 16 == 0 and S.out_ch[0] == 32 and S.in_ch == 3
-                and self.topo.spiral_flat[0] is not None)
-
     def _flat_dx(self, b, lv, cin, cout):
         """The flat-list bf16 data gradient applies (vertex-major level,
         batch a multiple of 16, 32 -> 32/64 channels, fan-in <= 20)."""
@@ -890,78 +771,13 @@ class SDVAEEngine:
         still-deferred conv weight gradient -- with ``fuse_adam`` (nothing
         exchanges the gradient before the update) the Adam step runs in the
         same launch (``cfsd_dw_reduce_batch_adam``) and adam_step is skipped."""
-        T, S, P = self.topo, self.spec, self.params
+        T = self.topo
         deferred, b.deferred = b.deferred, []
-
-        def defer(d, name):
-            deferred.append((d, P.gview(name + ".weight"), P.gview(name + ".bias")))
-
-        weight_grad = ops.spiral_conv_bwd_weight
-        for (cin, cout, lv) in reversed(S.enc_layers()):
-            w, _ = self._enc_w(lv)
-            x_in = b.x if lv == 0 else b.enc_out[lv - 1]
-            rows_tab = T.enc_rows[lv]
-            prev = lv - 1
-            if lv in b.xl and b.rowsub_vm.get(("enc", lv)) and T.enc_select[prev]:
-                pass  # fp32 vertex-major x / dx: the paired row-subset launch below
-            elif (lv in b.xl and self.rowsub_pair16 and lv > 0 and b.rowsub_x.get(lv) and T.enc_select[prev]
-                  and x_in.dtype == torch.bfloat16 and b.dpre_enc[lv].dtype == torch.float32 and cin == 32
-                  and cout == 32 and b.bsz % 16 == 0 and T.enc_flat[lv][1] <= 16):
-                # bf16 Enblock: its flat dx and dW slabs in one launch
-                defer(ops.spiral_conv_bwd_rowsub_pair_bf16(x_in, rows_tab, b.dpre_enc[lv], T.enc_flat[lv], w,
-                                                           b.dpre_enc[prev], elu_y=b.enc_out[prev],
-                                                           workspace=b.ws_dw[("enc", lv)]),
-                      f"en_layers.{lv}.conv.layer")
-                continue
-            elif lv in b.xl:  # vertex-major (bf16 or fp32) operands (selection down-sampling)
-                defer(ops.spiral_conv_bwd_weight_x(x_in, rows_tab, b.dpre_enc[lv], None, None,
-                                                   b.ws_dw[("enc", lv)]), f"en_layers.{lv}.conv.layer")
-                if lv > 0 and b.dpre_enc[lv].dtype == torch.float32 and b.rowsub_x.get(lv):
-                    # fp32 dpre: dG = dpre.W at the kept rows (fp32), then the
-                    # flat gather rounded once to bf16
-                    ops.spiral_conv_bwd_data_rowsub(b.dpre_enc[lv], T.enc_flat[lv], w, T.n_verts[lv],
-                                                    elu_y=b.enc_out[prev], out=b.dpre_enc[prev],
-                                                    workspace=b.ws)
-                elif lv > 0:
-                    ops.spiral_conv_bwd_data_x(b.dpre_enc[lv], T.enc_inv[lv],
-                                               self._w16(f"en_layers.{lv}.conv.layer.weight"), T.n_verts[lv],
-                                               elu_y=b.enc_out[prev], out=b.dpre_enc[prev])
-                continue
-            if b.rowsub[("enc", lv)]:  # dG at the kept rows (+ dW slabs), then the flat gather
-                sel = T.enc_select[prev]
-                _, d = ops.spiral_conv_bwd_rowsub(x_in, rows_tab, b.dpre_enc[lv], T.enc_flat[lv], w, None, None,
-                                                  dx=b.dpre_enc[prev] if sel else b.g_pooled[prev],
-                                                  elu_y=b.enc_out[prev] if sel else None,
-                                                  workspace=b.ws_dw[("enc", lv)])
-                defer(d, f"en_layers.{lv}.conv.layer")
-                if not sel:
-                    ops.spmm(T.downT_csr[prev], b.g_pooled[prev], T.n_verts[prev],
-                             elu_y=b.enc_full[prev], out=b.dpre_enc[prev])
-                continue
-            if b.paired[("enc", lv)]:  # dx + dW slabs in one launch
-                sel = T.enc_select[prev]
-                _, d = ops.spiral_conv_bwd(x_in, rows_tab, b.dpre_enc[lv], T.enc_inv[lv], w, None, None,
-                                           dx=b.dpre_enc[prev] if sel else b.g_pooled[prev],
-                                           elu_y=b.enc_out[prev] if sel else None,
-                                           workspace=b.ws_dw[("enc", lv)])
-                defer(d, f"en_layers.{lv}.conv.layer")
-                if not sel:
-                    ops.spmm(T.downT_csr[prev], b.g_pooled[prev], T.n_verts[prev],
-                             elu_y=b.enc_full[prev], out=b.dpre_enc[prev])
-                continue
-            defer(weight_grad(x_in, rows_tab, b.dpre_enc[lv], None, None,
-                              b.ws_dw[("enc", lv)]), f"en_layers.{lv}.conv.layer")
-            if lv == 0:
-                break
-            if T.enc_select[prev]:
-                # input of this conv IS the ELU output of the previous Enblock
-                ops.spiral_conv_bwd_data(b.dpre_enc[lv], T.enc_inv[lv], w, T.n_verts[lv],
-                                         elu_y=b.enc_out[prev], out=b.dpre_enc[prev], workspace=b.ws)
-            else:
-                ops.spiral_conv_bwd_data(b.dpre_enc[lv], T.enc_inv[lv], w, T.n_verts[lv],
-                                         out=b.g_pooled[prev], workspace=b.ws)
-                ops.spmm(T.downT_csr[prev], b.g_pooled[prev], T.n_verts[prev], elu_y=b.enc_full[prev],
-                         out=b.dpre_enc[prev])
+        for lv in reversed(range(self.spec.n)):
+            b.plan["enc", lv].run(self, b, deferred)
+            if lv > 0 and not T.enc_select[lv - 1]:  # through Pool(down) into the previous Enblock's ELU
+                ops.spmm(T.downT_csr[lv - 1], b.g_pooled[lv - 1], T.n_verts[lv - 1], elu_y=b.enc_full[lv - 1],
+                         out=b.dpre_enc[lv - 1])
         ops.dw_reduce_batch(deferred, adam=self.adam_args() if fuse_adam else None)
 
     def adam_step(self, grad_scale=None):

@@ -137,6 +137,20 @@ def torus_topology(nu=NU, nv=NV, factors=(4, 4, 4), seq=SEQ, n_regions=N_REGIONS
     return npz
 
 
+def averaging_down(npz, levels):
+    """Copy of ``npz`` whose ``down_l`` of every level in ``levels`` is no 0/1
+    selection: kept vertex k becomes 0.5 * k + 0.5 * ((k + 1) mod n) (the
+    general Pool(down) path; the shapes stay)."""
+    out = dict(npz)
+    for l in levels:
+        keep = np.asarray(npz[f"down_{l}_col"], np.int64)
+        n = int(npz[f"down_{l}_shape"][1])
+        out[f"down_{l}_row"] = np.repeat(np.arange(len(keep), dtype=np.int64), 2)
+        out[f"down_{l}_col"] = np.stack([keep, (keep + 1) % n], 1).reshape(-1)
+        out[f"down_{l}_val"] = np.full(2 * len(keep), 0.5, np.float32)
+    return out
+
+
 def torus_meshes(n, nu=NU, nv=NV, seed=0):
     """``n`` deformed tori (smooth random bumps), normalised-scale fp32."""
     pos, _ = torus_grid(nu, nv)
