@@ -260,6 +260,30 @@ class ModelManager:
         self.net.train()
         return self.net.decode(z.to(self.device))
 
+    def fit_mesh(self, verts, landmarks, landmark_idx, norm, latent_stats, **kw):
+        """``Tester.fit_mesh`` (``test.py:336-443``): fit the decoder to an
+        unregistered scan.  ``verts`` ``[P, 3]`` the scan's vertices (any
+        order), ``landmarks`` ``[L, 3]`` points on it, ``landmark_idx`` the
+        ``L`` template vertices they correspond to, ``norm`` the ``norm.pt``
+        dictionary (``mean`` / ``std``; None for un-normalised data),
+        ``latent_stats`` the ``z_stats.pt`` dictionary (``means``).  The scan
+        is aligned to the template (:func:`fitting.procrustes_align`), then
+        :func:`fitting.fit_points` runs over :meth:`generate_for_opt`
+        (``**kw``: its options).  Returns ``(FitResult, aligned_verts)``;
+        the result's errors and histories are multiplied by ``to_mm_const``."""
+        from . import fitting
+        lidx = np.asarray(landmark_idx, np.int64).reshape(-1)
+        aligned, aligned_lnd = fitting.procrustes_align(landmarks, self.template.pos[lidx], verts)
+        use_norm = norm is not None and self._normalized_data
+        res = fitting.fit_points(
+            self.generate_for_opt, torch.as_tensor(aligned, dtype=torch.float32).to(self.device),
+            torch.as_tensor(aligned_lnd, dtype=torch.float32), lidx,
+            norm["mean"] if use_norm else None, norm["std"] if use_norm else None,
+            latent_stats["means"], module=self.net, **kw)
+        for name in ("errors_shape", "errors_lnd", "chamfer_history", "landmark_history"):
+            setattr(res, name, getattr(res, name) * self.to_mm_const)
+        return res, aligned
+
     def encode(self, x):
         """Eval-mode latents of device meshes [N, V, 3] (model_manager.py:243-246)."""
         return self.engine.encode_all(x, batch_size=self.bs * self.bs)

@@ -882,6 +882,133 @@ def reconstruction_error_stats(mesh_means):
             "max": torch.max(mesh_means).item(), "std": torch.std(mesh_means).item()}
 
 
+# ------------------------------------------------------------------ latent fitting
+NN_TILE = 16  # CFSD_NN_TILE: reference points per chunk of cfsd_nn_points (include/cfsd.h)
+
+
+def _points(t, name):
+    _need(t, None, name=name)
+    if t.dim() != 3 or t.shape[-1] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected [B, N >= 1, 3]")
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def _pair_batch(bq, br, what):
+    bsz = max(bq, br)
+    if bq not in (1, bsz) or br not in (1, bsz):
+        raise ValueError(f"{what}: batch sizes {bq} and {br} must be equal or 1")
+    return bsz
+
+
+def nn_points(q, r, workspace=None):
+    """Brute-force nearest neighbour (``cfsd_nn_points``): for every query of
+    ``q`` ``[Bq, N, 3]`` the squared distance to, and the int32 index of, the
+    nearest point of ``r`` ``[Br, P, 3]``.  ``Bq`` and ``Br`` are equal or 1; a
+    batch of 1 is shared by every element of the other operand's batch (read
+    in place, not expanded).  Equal distances resolve to the lowest index.
+    Returns ``(dist2 [B, N] float32, idx [B, N] int32)``."""
+    bq, n = _points(q, "q")
+    br, p = _points(r, "r")
+    if r.device != q.device:
+        raise ValueError("q and r must be on one device")
+    bsz = _pair_batch(bq, br, "nn_points")
+    need = int(_abi.lib().cfsd_nn_points_workspace(bsz, n, p))
+    nbytes = 0
+    if need:
+        workspace, nbytes = _conv_ws(workspace, q.device, need)
+    else:
+        workspace = None
+    dist2 = torch.empty((bsz, n), dtype=torch.float32, device=q.device)
+    idx = torch.empty((bsz, n), dtype=torch.int32, device=q.device)
+    call("cfsd_nn_points", ptr(q), ptr(r), ptr(dist2), ptr(idx), ptr(workspace), nbytes, bsz, bq, br, n, p,
+         stream_ptr())
+    return dist2, idx
+
+
+def chamfer_bwd(x, y, idx_xy, idx_yx, wx, wy):
+    """Gradient of the two-sided Chamfer sum w.r.t. ``x`` (``cfsd_chamfer_bwd``):
+    ``gx[b,i] = wx[b] 2(x_i - y[idx_xy[b,i]]) + wy[b] sum_{j: idx_yx[b,j]=i} 2(x_i - y_j)``.
+    The targets of each generated point are grouped on the device (stable
+    sort of ``idx_yx`` + segment offsets) and summed in ascending ``j`` by the
+    kernel: deterministic, no atomics."""
+    bsz, n = _points(x, "x")
+    by, p = _points(y, "y")
+    if by not in (1, bsz):
+        raise ValueError(f"chamfer_bwd: y batch {by} must be 1 or {bsz}")
+    _need(idx_xy, (bsz, n), torch.int32, "idx_xy")
+    _need(idx_yx, (bsz, p), torch.int32, "idx_yx")
+    _need(wx, (bsz,), name="wx")
+    _need(wy, (bsz,), name="wy")
+    keys, order = torch.sort(idx_yx, dim=1, stable=True)
+    bounds = torch.arange(n + 1, dtype=torch.int32, device=x.device).expand(bsz, n + 1).contiguous()
+    seg_ptr = torch.searchsorted(keys, bounds, out_int32=True).contiguous()
+    seg_j = order.to(torch.int32).contiguous()
+    gx = torch.empty_like(x)
+    call("cfsd_chamfer_bwd", ptr(x), ptr(y), ptr(idx_xy), ptr(seg_ptr), ptr(seg_j), ptr(wx), ptr(wy), ptr(gx),
+         bsz, by, n, p, stream_ptr())
+    return gx
+
+
+class _ChamferFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, point_mean):
+        d_xy, i_xy = nn_points(x, y)
+        d_yx, i_yx = nn_points(y, x)
+        ctx.save_for_backward(x, y, i_xy, i_yx)
+        ctx.point_mean = point_mean
+        cx, cy = d_xy.sum(1), d_yx.sum(1)
+        if point_mean:
+            cx, cy = cx / x.shape[1], cy / y.shape[1]
+        return cx + cy  # [B]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, i_xy, i_yx = ctx.saved_tensors
+        g = g.contiguous().to(torch.float32)
+        wx = g / x.shape[1] if ctx.point_mean else g
+        wy = g / y.shape[1] if ctx.point_mean else g.clone()
+        return chamfer_bwd(x, y, i_xy, i_yx, wx.contiguous(), wy.contiguous()), None, None
+
+
+def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None,
+                     batch_reduction="mean", point_reduction="mean", norm=2):
+    """The subset of ``pytorch3d.loss.chamfer_distance`` the reference's
+    fitting uses (``test.py:404-405, 427-429``), on libcfsd.
+
+    ``x`` ``[B, N, 3]`` generated points (may require grad), ``y`` ``[B or 1,
+    P, 3]`` target points (constant).  Per batch element: the mean (or sum)
+    over ``x`` of the squared distance to the nearest ``y``, plus the same from
+    ``y`` to ``x``; then ``batch_reduction`` ``"mean"``, ``"sum"`` or ``None``
+    (``[B]``).  Lengths, normals, weights and other norms raise
+    ``ValueError``.  Returns ``(loss, None)`` like pytorch3d (no normals
+    term)."""
+    if x_lengths is not None or y_lengths is not None:
+        raise ValueError("chamfer_distance: x_lengths / y_lengths are not supported (dense point sets only)")
+    if x_normals is not None or y_normals is not None:
+        raise ValueError("chamfer_distance: normals are not supported")
+    if weights is not None:
+        raise ValueError("chamfer_distance: weights are not supported")
+    if norm != 2:
+        raise ValueError("chamfer_distance: only norm=2 (squared L2) is supported")
+    if batch_reduction not in ("mean", "sum", None):
+        raise ValueError('batch_reduction must be one of ["mean", "sum"] or None')
+    if point_reduction not in ("mean", "sum"):
+        raise ValueError('point_reduction must be one of ["mean", "sum"]')
+    if y.requires_grad:
+        raise ValueError("chamfer_distance: the target y is a constant (no gradient is computed for it)")
+    x, y = x.contiguous(), y.contiguous()
+    bsz, _ = _points(x, "x")
+    by, _ = _points(y, "y")
+    if by not in (1, bsz):
+        raise ValueError(f"chamfer_distance: y batch {by} must be 1 or {bsz}")
+    per_batch = _ChamferFn.apply(x, y, point_reduction == "mean")
+    if batch_reduction == "mean":
+        return per_batch.sum() / bsz, None
+    if batch_reduction == "sum":
+        return per_batch.sum(), None
+    return per_batch, None
+
+
 # ------------------------------------------------------------------ bf16 path
 # Mixed-precision entry points (include/cfsd.h "bf16 path"): activations /
 # gradients are float32 or bfloat16 tensors, weights are the fp32 master view

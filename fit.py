@@ -1,0 +1,15 @@
+"""``python fit.py --config C --checkpoint-dir D --mesh scan.obj --landmarks
+lm.json --template-landmarks idx.json --z-stats z_stats.pt --out PREFIX``: fit
+a trained model to an unregistered scan (the reference's Tester.fit_mesh,
+test.py:336-520) on the MI355X path (craniofacialsd-vae_amd/fitting.py)."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cfsd_loader  # noqa: E402
+
+cfsd_loader.load()
+from craniofacialsd_vae_amd.fitting import fit_main  # noqa: E402
+
+if __name__ == "__main__":
+    fit_main()

@@ -607,6 +607,42 @@ int cfsd_vertex_errors(const float* out, const float* gt, const float* mean, con
                        float* err, float* l1, float* mesh_mean, int batch, int nv, float to_mm,
                        void* stream);
 
+/* ---------------------------------------------------------------- latent fitting
+ * The Chamfer term of Tester.fit_mesh (test.py:404-405, 427-429:
+ * pytorch3d.loss.chamfer_distance between the decoded heads and an
+ * unregistered scan), ABI 4.13.
+ *
+ * cfsd_nn_points: batched brute-force nearest neighbour.  q [bq, n, 3] queries,
+ * r [br, p, 3] reference points, fp32; bq and br are each 1 or `batch` (1 =
+ * the one set is shared by every batch element, read in place).  Per query
+ *   dist2[b, i] = min_j |q[b,i] - r[b,j]|^2,  idx[b, i] = the arg min (int32),
+ * the distance in difference form (dx*dx + dy*dy + dz*dz, d = q - r; no
+ * |q|^2 + |r|^2 - 2 q.r expansion), bit-equal distances resolved to the
+ * lowest j.  No atomics; the values do not depend on the launch geometry.
+ * The reference points are walked in chunks of CFSD_NN_TILE; a partial last
+ * chunk visits only the points that exist.  n, p >= 1.
+ * workspace: cfsd_nn_points_workspace() bytes (0 = none needed, NULL allowed):
+ * with few queries the reference range is cut into segments whose winners
+ * are merged there. */
+#define CFSD_NN_TILE 16
+size_t cfsd_nn_points_workspace(int batch, int n, int p);
+int cfsd_nn_points(const float* q, const float* r, float* dist2, int32_t* idx, void* workspace,
+                   size_t workspace_bytes, int batch, int bq, int br, int n, int p, void* stream);
+
+/* Gradient of the two-sided Chamfer sum with respect to the generated points
+ * x [batch, n, 3] only (the target y [by, p, 3], by = 1 or batch, is constant):
+ *   gx[b,i] = wx[b] 2 (x_i - y[idx_xy[b,i]]) + wy[b] sum_{j: idx_yx[b,j] = i} 2 (x_i - y_j)
+ * idx_xy [batch, n] from cfsd_nn_points(x, y); the other direction's
+ * idx_yx [batch, p] (cfsd_nn_points(y, x)) is passed GROUPED by generated
+ * point: seg_j [batch, p] = the targets j of batch b ordered by (idx_yx[b,j], j)
+ * (a stable sort), seg_ptr [batch, n + 1] = the offsets of each i's run in it.
+ * Each run is summed in ascending j by one thread: deterministic, no atomics.
+ * wx, wy [batch] device floats fold in the upstream gradient and the 1/n,
+ * 1/p, 1/batch of the reductions.  Indices are clamped into range. */
+int cfsd_chamfer_bwd(const float* x, const float* y, const int32_t* idx_xy, const int32_t* seg_ptr,
+                     const int32_t* seg_j, const float* wx, const float* wy, float* gx, int batch, int by,
+                     int n, int p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
