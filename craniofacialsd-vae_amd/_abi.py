@@ -109,6 +109,9 @@ SIGNATURES = {
     "cfsd_nn_points_workspace": (_Z, [_I, _I, _I]),
     "cfsd_nn_points": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P]),
     "cfsd_chamfer_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "cfsd_point_face_workspace": (_Z, [_I, _I]),
+    "cfsd_point_face": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "cfsd_point_face_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
 }
 
 

@@ -145,6 +145,33 @@ def read_obj_vertices(path):
     return np.asarray(vs, np.float64)
 
 
+def read_obj_faces(path, n_verts=None):
+    """Triangles of an OBJ file, ``[F, 3]`` int64, zero-based: ``f`` lines in
+    the ``a``, ``a/b``, ``a/b/c`` and ``a//c`` forms (the vertex index is the
+    first field), negative indices counted back from the vertices read so far,
+    polygons triangulated as a fan around their first corner.  ``n_verts``
+    (optional) checks every index against the vertex count."""
+    faces, seen = [], 0
+    with open(path) as f:
+        for no, ln in enumerate(f, 1):
+            if ln.startswith("v "):
+                seen += 1
+            elif ln.startswith("f "):
+                idx = []
+                for tok in ln.split()[1:]:
+                    i = int(tok.split("/")[0])
+                    if i == 0:
+                        raise ValueError(f"{path}:{no}: OBJ indices are 1-based, got 0")
+                    idx.append(i - 1 if i > 0 else seen + i)
+                if len(idx) < 3:
+                    raise ValueError(f"{path}:{no}: a face needs at least 3 corners")
+                faces += [[idx[0], idx[k], idx[k + 1]] for k in range(1, len(idx) - 1)]
+    out = np.asarray(faces, np.int64).reshape(-1, 3)
+    if n_verts is not None and out.size and (out.min() < 0 or out.max() >= n_verts):
+        raise ValueError(f"{path}: face indices span [{out.min()}, {out.max()}], outside [0, {n_verts})")
+    return out
+
+
 def write_obj(path, verts, faces=None):
     """OBJ with ``v`` lines (9 significant digits: fp32 round-trips) and
     1-based ``f`` lines (what ``mesh1.export`` of the augmented mesh writes,

@@ -9,7 +9,10 @@ landmarks on it, find the latent code whose decoded head matches the scan:
 2. :func:`fit_points` -- ``n_starts`` latent codes optimised together with
    Adam on ``10 * landmark MSE + Chamfer distance`` (``test.py:381-443``);
    the Chamfer term is :func:`ops.chamfer_distance` (HIP nearest-neighbour
-   search; pytorch3d has no ROCm build), the decoder runs through
+   search; pytorch3d has no ROCm build) or, when the scan's and the
+   template's faces are given, :func:`ops.surface_distance` (HIP
+   point-to-triangle search: the distance to the SURFACES, free of the
+   vertex-to-vertex term's sampling floor); the decoder runs through
    ``model.py``'s autograd Functions with its parameters frozen, which
    selects their data-gradient-only backward;
 3. :func:`fit_main` -- the ``fit.py`` command line.
@@ -78,6 +81,9 @@ class FitResult:
     chamfer_history: torch.Tensor    # [iterations] the Chamfer term (mean over the starts)
     landmark_history: torch.Tensor   # [iterations] the landmark MSE (mean over the starts)
     best: int
+    # with faces (the surface path): the mean UNSQUARED distance of the scan's vertices to the best fitted
+    # head's surface, a 0-d device tensor; errors_shape and chamfer_history then hold the surface term
+    surface_mm: torch.Tensor = None
 
 
 @contextlib.contextmanager
@@ -103,7 +109,7 @@ def frozen(module):
 
 def fit_points(decode, target_points, target_landmarks, landmark_idx, mean, std, latent_mean, latent_std=None,
                n_starts=16, lr=5e-3, iterations=250, seed=0, selection_weights=(10.0, 1.0), landmark_weight=10.0,
-               module=None):
+               module=None, target_faces=None, template_faces=None):
     """The optimisation loop of ``Tester.fit_mesh`` (``test.py:381-443``).
 
     ``decode(z [n_starts, latent]) -> [n_starts, V, 3]`` with autograd (e.g.
@@ -128,6 +134,12 @@ def fit_points(decode, target_points, target_landmarks, landmark_idx, mean, std,
     ``requires_grad`` flags and the train / eval modes are restored in a
     ``finally``.
 
+    ``target_faces`` ``[Fs, 3]`` (the scan's triangles) and ``template_faces``
+    ``[F, 3]`` (the decoded heads'), device int32, given TOGETHER replace the
+    Chamfer term by ``ops.surface_distance(gen, template_faces, target,
+    target_faces)`` in the loss, in ``errors_shape`` and in the history, and
+    fill ``surface_mm``; without them the loop is the vertex path unchanged.
+
     The best start is the argmin of ``w0 * errors_lnd + w1 * errors_shape``
     with ``selection_weights = (w0, w1)``.  The reference (``test.py:442``)
     computes ``10 * errors_lnd + errors_lnd``: the landmark error twice and
@@ -141,6 +153,8 @@ def fit_points(decode, target_points, target_landmarks, landmark_idx, mean, std,
         raise ValueError("fit_points: mean and std go together")
     if module is None and isinstance(getattr(decode, "__self__", None), torch.nn.Module):
         module = decode.__self__
+    if (target_faces is None) != (template_faces is None):
+        raise ValueError("fit_points: target_faces and template_faces go together")
     dev = target_points.device
     target = target_points.detach().to(torch.float32).reshape(1, -1, 3).contiguous()
     lnd = target_landmarks.detach().to(dev, torch.float32).reshape(1, -1, 3)
@@ -161,6 +175,14 @@ def fit_points(decode, target_points, target_landmarks, landmark_idx, mean, std,
     ch_hist = torch.zeros(iterations, dtype=torch.float32, device=dev)
     lnd_hist = torch.zeros(iterations, dtype=torch.float32, device=dev)
     verts = None
+    scan = None if target_faces is None else ops.SurfaceMesh(target, target_faces)
+
+    def shape_term(v, batch_reduction="mean"):
+        if scan is None:
+            return ops.chamfer_distance(v, target, batch_reduction=batch_reduction)[0]
+        return ops.surface_distance(v, template_faces, scan, batch_reduction=batch_reduction)
+
+    surface_mm = None
     with frozen(module):
         for it in range(iterations):
             opt.zero_grad()
@@ -168,20 +190,24 @@ def fit_points(decode, target_points, target_landmarks, landmark_idx, mean, std,
             if mean is not None:
                 verts = verts * std + mean
             lnd_loss = torch.mean((torch.index_select(verts, 1, lidx) - lnd) ** 2)
-            ch_loss = ops.chamfer_distance(verts, target)[0]
+            ch_loss = shape_term(verts)
             (landmark_weight * lnd_loss + ch_loss).backward()
             opt.step()
             ch_hist[it] = ch_loss.detach()
             lnd_hist[it] = lnd_loss.detach()
         with torch.no_grad():
             verts = verts.detach()
-            errors_shape = ops.chamfer_distance(verts, target, batch_reduction=None)[0]
+            errors_shape = shape_term(verts, batch_reduction=None)
             errors_lnd = torch.mean(((verts[:, lidx, :] - lnd) ** 2).reshape(n_starts, -1), dim=1)
             w0, w1 = selection_weights
             best = int(torch.argmin(w0 * errors_lnd + w1 * errors_shape).item())  # the one host read
+            if scan is not None:
+                surface_mm = ops.point_mesh_distance(scan.queries, verts[best][None].contiguous(),
+                                                     template_faces).sqrt().mean()
     z_all = z.detach()
     return FitResult(verts=verts[best], z=z_all[best], z_all=z_all, z_init=z_init, errors_shape=errors_shape,
-                     errors_lnd=errors_lnd, chamfer_history=ch_hist, landmark_history=lnd_hist, best=best)
+                     errors_lnd=errors_lnd, chamfer_history=ch_hist, landmark_history=lnd_hist, best=best,
+                     surface_mm=surface_mm)
 
 
 # ------------------------------------------------------------------ command line
@@ -195,7 +221,9 @@ def fit_main(argv=None):
     """``fit.py``: fit a trained model to ``--mesh`` and write
     ``<out>_fit.obj`` (the fitted head, template faces), ``<out>_aligned.obj``
     (the aligned scan) and one JSON line with the errors (mm) and the best
-    latent."""
+    latent.  ``--surface`` reads the scan's faces too and fits to its
+    triangles (:func:`ops.surface_distance`): the line then carries
+    ``surface_mm`` and the aligned scan is written with its faces."""
     import argparse
     import os
 
@@ -212,6 +240,8 @@ def fit_main(argv=None):
     parser.add_argument("--lr", type=float, default=5e-3)
     parser.add_argument("--n-starts", type=int, default=16)
     parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--surface", action="store_true",
+                        help="fit to the scan's triangles (its f lines), not its vertices")
     opts = parser.parse_args(argv)
 
     from . import data as D
@@ -228,12 +258,21 @@ def fit_main(argv=None):
         norm = torch.load(os.path.join(config["data"]["precomputed_path"], "norm.pt"), weights_only=True)
     with open(opts.template_landmarks) as f:
         landmark_idx = [int(i) for i in json.load(f)]
-    res, aligned = manager.fit_mesh(D.read_obj_vertices(opts.mesh), read_landmarks(opts.landmarks), landmark_idx,
-                                    norm, torch.load(opts.z_stats, weights_only=True), lr=opts.lr,
+    scan = D.read_obj_vertices(opts.mesh)
+    faces = None
+    if opts.surface:
+        faces = D.read_obj_faces(opts.mesh, n_verts=len(scan))
+        if not len(faces):
+            raise ValueError(f"--surface: {opts.mesh} has no faces")
+    res, aligned = manager.fit_mesh(scan, read_landmarks(opts.landmarks), landmark_idx,
+                                    norm, torch.load(opts.z_stats, weights_only=True), faces=faces, lr=opts.lr,
                                     iterations=opts.iterations, n_starts=opts.n_starts, seed=opts.seed)
     D.write_obj(opts.out + "_fit.obj", res.verts.cpu().numpy(), manager.template.faces)
-    D.write_obj(opts.out + "_aligned.obj", aligned)
-    line = {"best": res.best, "chamfer_mm": float(res.errors_shape[res.best]),
+    D.write_obj(opts.out + "_aligned.obj", aligned, faces)
+    shape_key = "surface_term_mm" if opts.surface else "chamfer_mm"
+    line = {"best": res.best, shape_key: float(res.errors_shape[res.best]),
             "landmark_mm": float(res.errors_lnd[res.best]), "z": res.z.cpu().tolist()}
+    if opts.surface:
+        line["surface_mm"] = float(res.surface_mm)
     print(json.dumps(line))
     return line

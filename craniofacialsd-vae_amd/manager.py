@@ -260,7 +260,7 @@ class ModelManager:
         self.net.train()
         return self.net.decode(z.to(self.device))
 
-    def fit_mesh(self, verts, landmarks, landmark_idx, norm, latent_stats, **kw):
+    def fit_mesh(self, verts, landmarks, landmark_idx, norm, latent_stats, faces=None, **kw):
         """``Tester.fit_mesh`` (``test.py:336-443``): fit the decoder to an
         unregistered scan.  ``verts`` ``[P, 3]`` the scan's vertices (any
         order), ``landmarks`` ``[L, 3]`` points on it, ``landmark_idx`` the
@@ -269,9 +269,17 @@ class ModelManager:
         ``latent_stats`` the ``z_stats.pt`` dictionary (``means``).  The scan
         is aligned to the template (:func:`fitting.procrustes_align`), then
         :func:`fitting.fit_points` runs over :meth:`generate_for_opt`
-        (``**kw``: its options).  Returns ``(FitResult, aligned_verts)``;
-        the result's errors and histories are multiplied by ``to_mm_const``."""
+        (``**kw``: its options).  ``faces`` ``[Fs, 3]`` (the scan's triangles,
+        zero-based) switches the shape term to the distance between the
+        SURFACES of the scan and of the decoded heads (the template's faces)
+        and fills ``surface_mm``.  Returns ``(FitResult, aligned_verts)``;
+        the result's errors, histories and ``surface_mm`` are multiplied by
+        ``to_mm_const``."""
         from . import fitting
+        if faces is not None:
+            kw["target_faces"] = torch.as_tensor(np.asarray(faces, np.int64), dtype=torch.int32).to(self.device)
+            kw["template_faces"] = torch.as_tensor(np.asarray(self.template.faces, np.int64),
+                                                   dtype=torch.int32).to(self.device)
         lidx = np.asarray(landmark_idx, np.int64).reshape(-1)
         aligned, aligned_lnd = fitting.procrustes_align(landmarks, self.template.pos[lidx], verts)
         use_norm = norm is not None and self._normalized_data
@@ -282,6 +290,8 @@ class ModelManager:
             latent_stats["means"], module=self.net, **kw)
         for name in ("errors_shape", "errors_lnd", "chamfer_history", "landmark_history"):
             setattr(res, name, getattr(res, name) * self.to_mm_const)
+        if res.surface_mm is not None:
+            res.surface_mm = res.surface_mm * self.to_mm_const
         return res, aligned
 
     def encode(self, x):

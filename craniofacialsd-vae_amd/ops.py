@@ -1009,6 +1009,264 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_nor
     return per_batch, None
 
 
+# ------------------------------------------------------------------ surface fitting
+PF_GROUP = 16      # CFSD_PF_GROUP: faces per group sphere of cfsd_point_face (include/cfsd.h)
+PF_CULL = 1        # CFSD_PF_CULL
+PF_PREPARED = 2    # CFSD_PF_PREPARED
+PF_WAVE = 64       # queries per workgroup of cfsd_point_face: one row of its stats
+
+
+class FaceTable:
+    """A validated ``[F, 3]`` int32 face tensor of a mesh with ``n_verts``
+    vertices, and what seeds the culled search: ``ref_idx`` ``[R]`` the
+    vertices some face references (ascending) and ``vert_face`` ``[R]`` int32
+    the lowest face at each.  Built by :func:`face_table`."""
+
+    def __init__(self, faces, n_verts):
+        _need(faces, None, torch.int32, "faces")
+        if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+            raise ValueError(f"faces: shape {tuple(faces.shape)}, expected [F >= 1, 3]")
+        lo, hi = torch.aminmax(faces)
+        lo, hi = int(lo), int(hi)  # the one host read, once per face tensor
+        if lo < 0 or hi >= n_verts:
+            raise ValueError(f"faces: indices span [{lo}, {hi}], outside [0, {n_verts})")
+        nf = int(faces.shape[0])
+        fid = torch.arange(nf, device=faces.device).repeat_interleave(3)
+        first = torch.full((n_verts,), nf, dtype=torch.long, device=faces.device)
+        first.scatter_reduce_(0, faces.reshape(-1).long(), fid, "amin")
+        self.faces, self.n_verts, self.n_faces = faces, int(n_verts), nf
+        self.ref_idx = torch.nonzero(first < nf).reshape(-1)
+        self.vert_face = first[self.ref_idx].to(torch.int32)
+
+
+_FACE_TABLES = {}  # (data_ptr, version, F, n_verts, device) -> FaceTable (holds the tensor: the key stays its own)
+
+
+def face_table(faces, n_verts):
+    """The :class:`FaceTable` of ``faces``.  Host tensors, wrong ranks or
+    dtypes and indices outside ``[0, n_verts)`` raise ``ValueError``; the
+    index check reads the device once per face tensor (the few most recent
+    tables are kept, keyed by the tensor's storage and version)."""
+    if isinstance(faces, FaceTable):
+        if faces.n_verts != n_verts:
+            raise ValueError(f"faces: table built for {faces.n_verts} vertices, mesh has {n_verts}")
+        return faces
+    if not isinstance(faces, torch.Tensor):
+        raise ValueError("faces must be a device int32 tensor [F, 3]")
+    key = (faces.data_ptr(), faces._version, tuple(faces.shape), faces.dtype, int(n_verts), str(faces.device))
+    tab = _FACE_TABLES.pop(key, None)
+    if tab is None:
+        tab = FaceTable(faces, int(n_verts))
+    _FACE_TABLES[key] = tab  # most recent last
+    while len(_FACE_TABLES) > 8:
+        _FACE_TABLES.pop(next(iter(_FACE_TABLES)))
+    return tab
+
+
+def _morton_order(p):
+    """Permutation of the points ``p`` ``[P, 3]`` along a 30-bit Morton curve
+    of their bounding box (device only, no host read): consecutive points are
+    neighbours in space, whatever order the file listed them in."""
+    lo, hi = p.min(0).values, p.max(0).values
+    q = ((p - lo) / (hi - lo).clamp_min(1e-30) * 1023.0).long().clamp_(0, 1023)
+
+    def spread(x):
+        x = (x | (x << 16)) & 0x030000FF
+        x = (x | (x << 8)) & 0x0300F00F
+        x = (x | (x << 4)) & 0x030C30C3
+        return (x | (x << 2)) & 0x09249249
+
+    return torch.argsort(spread(q[:, 0]) | (spread(q[:, 1]) << 1) | (spread(q[:, 2]) << 2), stable=True)
+
+
+class SurfaceMesh:
+    """A CONSTANT mesh as the target of repeated searches: ``verts`` ``[1, V,
+    3]``, its :class:`FaceTable`, its referenced vertices and the workspace
+    that keeps the per-face records of ``cfsd_point_face`` after the first
+    search, so that later ones skip the pre-launch.  ``queries`` ``[1, V, 3]``
+    are the same vertices in Morton order, for searches FROM the mesh: a wave
+    of ``cfsd_point_face`` culls for its 64 consecutive queries together, and
+    a scan's vertex order is arbitrary."""
+
+    def __init__(self, verts, faces):
+        verts = verts.detach()
+        if verts.dim() == 2:
+            verts = verts[None]
+        verts = verts.contiguous()
+        bv, nv = _points(verts, "verts")
+        if bv != 1:
+            raise ValueError(f"SurfaceMesh: one mesh expected, got a batch of {bv}")
+        self.verts, self.table = verts, face_table(faces, nv)
+        self.ref = verts.index_select(1, self.table.ref_idx).contiguous()
+        need = int(_abi.lib().cfsd_point_face_workspace(1, self.table.n_faces))
+        self.workspace = torch.empty(need // 4, dtype=torch.float32, device=verts.device)
+        self.prepared = False
+        self.queries = verts.index_select(1, _morton_order(verts[0])).contiguous()
+
+
+def point_face_distance(points, verts, faces=None, cull=True, return_stats=False):
+    """Nearest point of a triangle mesh (``cfsd_point_face``): for every point
+    of ``points`` ``[Bp, N, 3]`` the squared distance to the closed triangles
+    ``faces`` ``[F, 3]`` (int32, shared by the batch) of ``verts`` ``[Bv, V,
+    3]``, the int32 index of the nearest face (equal distances: the lowest)
+    and the barycentric weights of the nearest point on it.  ``Bp`` and ``Bv``
+    are equal or 1.  ``verts`` may be a :class:`SurfaceMesh` (then ``faces`` is
+    not given).
+
+    ``cull=True`` seeds every point's bound with a face at its nearest
+    referenced vertex (``nn_points`` over the vertices that a face uses) and
+    skips groups and faces whose bounding sphere is out of reach;
+    ``cull=False`` evaluates every pair.  The results are bit-identical.
+    Returns ``(dist2 [B, N] float32, face_idx [B, N] int32, bary [B, N, 3]
+    float32)``, with ``return_stats`` also ``[B * ceil(N / 64), 2]`` int32:
+    per wave of 64 points the groups entered and the faces evaluated."""
+    mesh = verts if isinstance(verts, SurfaceMesh) else None
+    if mesh is not None:
+        if faces is not None:
+            raise ValueError("point_face_distance: a SurfaceMesh carries its own faces")
+        verts, tab = mesh.verts, mesh.table
+    bp, n = _points(points, "points")
+    bv, nv = _points(verts, "verts")
+    if verts.device != points.device:
+        raise ValueError("points and verts must be on one device")
+    if mesh is None:
+        tab = face_table(faces, nv)
+    bsz = _pair_batch(bp, bv, "point_face_distance")
+    dev, nf = points.device, tab.n_faces
+    if mesh is not None:
+        workspace = mesh.workspace
+    else:
+        workspace = torch.empty(int(_abi.lib().cfsd_point_face_workspace(bv, nf)) // 4, dtype=torch.float32,
+                                device=dev)
+    flags, seed = 0, None
+    if cull:
+        flags |= PF_CULL
+        ref = mesh.ref if mesh is not None else verts.index_select(1, tab.ref_idx).contiguous()
+        seed = tab.vert_face[nn_points(points, ref)[1].long()].contiguous()
+    if mesh is not None and mesh.prepared:
+        flags |= PF_PREPARED
+    dist2 = torch.empty((bsz, n), dtype=torch.float32, device=dev)
+    face_idx = torch.empty((bsz, n), dtype=torch.int32, device=dev)
+    bary = torch.empty((bsz, n, 3), dtype=torch.float32, device=dev)
+    stats = None
+    if return_stats:
+        stats = torch.empty((bsz * ((n + PF_WAVE - 1) // PF_WAVE), 2), dtype=torch.int32, device=dev)
+    call("cfsd_point_face", ptr(points), ptr(verts), ptr(tab.faces), ptr(seed), ptr(dist2), ptr(face_idx),
+         ptr(bary), ptr(stats), ptr(workspace), workspace.numel() * 4, bsz, bp, bv, n, nv, nf, flags, stream_ptr())
+    if mesh is not None:
+        mesh.prepared = True
+    return (dist2, face_idx, bary, stats) if return_stats else (dist2, face_idx, bary)
+
+
+def point_face_bwd(points, verts, faces, face_idx, bary, g, want_verts):
+    """Gradient of ``sum g * dist2`` through fixed faces and weights
+    (``cfsd_point_face_bwd``): ``gp [B, N, 3] = g 2 (p - c)`` and, with
+    ``want_verts``, ``gv [B, V, 3]``, each vertex's ``-gp * weight``
+    contributions grouped on the device (stable sort of the winning faces'
+    corners + run offsets) and summed in ascending order by one thread:
+    deterministic, no atomics.  Returns ``(gp, gv or None)`` at the full batch."""
+    bp, n = _points(points, "points")
+    bv, nv = _points(verts, "verts")
+    bsz = _pair_batch(bp, bv, "point_face_bwd")
+    tab = face_table(faces, nv)
+    _need(face_idx, (bsz, n), torch.int32, "face_idx")
+    _need(bary, (bsz, n, 3), name="bary")
+    _need(g, (bsz, n), name="g")
+    gp = torch.empty((bsz, n, 3), dtype=torch.float32, device=points.device)
+    seg_ptr = seg_e = gv = None
+    if want_verts:
+        corners = tab.faces[face_idx.long()].reshape(bsz, 3 * n)  # vertex of pair i * 3 + k
+        keys, order = torch.sort(corners, dim=1, stable=True)
+        bounds = torch.arange(nv + 1, dtype=torch.int32, device=points.device).expand(bsz, nv + 1).contiguous()
+        seg_ptr = torch.searchsorted(keys, bounds, out_int32=True).contiguous()
+        seg_e = order.to(torch.int32).contiguous()
+        gv = torch.empty((bsz, nv, 3), dtype=torch.float32, device=points.device)
+    call("cfsd_point_face_bwd", ptr(points), ptr(verts), ptr(tab.faces), ptr(face_idx), ptr(bary), ptr(g), ptr(gp),
+         ptr(seg_ptr), ptr(seg_e), ptr(gv), bsz, bp, bv, n, nv, tab.n_faces, stream_ptr())
+    return gp, gv
+
+
+class _PointMeshFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, verts, target):
+        """``target``: the mesh's SurfaceMesh (then ``verts`` is its tensor) or FaceTable."""
+        mesh = target if isinstance(target, SurfaceMesh) else None
+        dist2, face_idx, bary = point_face_distance(points, mesh if mesh is not None else verts,
+                                                    None if mesh is not None else target)
+        ctx.save_for_backward(points, verts, face_idx, bary)
+        ctx.table = target.table if mesh is not None else target
+        ctx.mark_non_differentiable(face_idx, bary)
+        return dist2, face_idx, bary
+
+    @staticmethod
+    def backward(ctx, g, _gi, _gb):
+        points, verts, face_idx, bary = ctx.saved_tensors
+        want_p, want_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gp, gv = point_face_bwd(points, verts, ctx.table, face_idx, bary, g.contiguous().to(torch.float32), want_v)
+        if want_p and points.shape[0] != gp.shape[0]:
+            gp = gp.sum(0, keepdim=True)
+        if want_v and verts.shape[0] != gv.shape[0]:
+            gv = gv.sum(0, keepdim=True)
+        return (gp if want_p else None), (gv if want_v else None), None
+
+
+def _mesh_operands(verts, faces, what):
+    """(verts tensor, SurfaceMesh or FaceTable) of a mesh given either way."""
+    if isinstance(verts, SurfaceMesh):
+        if faces is not None:
+            raise ValueError(f"{what}: a SurfaceMesh carries its own faces")
+        return verts.verts, verts
+    _, nv = _points(verts, "verts")
+    return verts, face_table(faces, nv)
+
+
+def point_mesh_distance(points, verts, faces=None, return_faces=False):
+    """Squared distance of every point to the surface of a mesh, ``[B, N]``,
+    differentiable in ``points`` and in ``verts`` (whichever requires grad)
+    through the nearest faces and weights found (``point_face_distance``'s
+    culled search; the backward is ``cfsd_point_face_bwd``).  ``verts`` may be
+    a :class:`SurfaceMesh` (a constant).  With ``return_faces`` also the face
+    indices and weights."""
+    _points(points, "points")
+    verts, target = _mesh_operands(verts, faces, "point_mesh_distance")
+    if verts.device != points.device:
+        raise ValueError("points and verts must be on one device")
+    dist2, face_idx, bary = _PointMeshFn.apply(points, verts, target)
+    return (dist2, face_idx, bary) if return_faces else dist2
+
+
+def surface_distance(gen_verts, gen_faces, scan_verts, scan_faces=None, batch_reduction="mean"):
+    """The surface term of the fit: per batch element the mean over the
+    generated vertices ``gen_verts`` ``[B, V, 3]`` of the squared distance to
+    the scan's surface, plus the mean over the scan's vertices of the squared
+    distance to the generated surface (``gen_faces`` ``[F, 3]``).  The scan is
+    a constant: ``scan_verts`` ``[1, P, 3]`` with ``scan_faces`` ``[Fs, 3]``,
+    or a :class:`SurfaceMesh` holding both (its per-face records, referenced
+    vertices and query order are then computed once, not per call).
+    ``batch_reduction`` ``"mean"``, ``"sum"`` or ``None``
+    (``[B]``), as in :func:`chamfer_distance`."""
+    if batch_reduction not in ("mean", "sum", None):
+        raise ValueError('batch_reduction must be one of ["mean", "sum"] or None')
+    if isinstance(scan_verts, SurfaceMesh):
+        if scan_faces is not None:
+            raise ValueError("surface_distance: a SurfaceMesh carries its own faces")
+        mesh = scan_verts
+    else:
+        if scan_verts.requires_grad:
+            raise ValueError("surface_distance: the scan is a constant (no gradient is computed for it)")
+        mesh = SurfaceMesh(scan_verts, scan_faces)
+    gen_verts = gen_verts.contiguous()
+    bsz, _ = _points(gen_verts, "gen_verts")
+    to_scan = point_mesh_distance(gen_verts, mesh)
+    to_gen = point_mesh_distance(mesh.queries, gen_verts, gen_faces)
+    per_batch = to_scan.mean(1) + to_gen.mean(1)
+    if batch_reduction == "mean":
+        return per_batch.sum() / bsz
+    if batch_reduction == "sum":
+        return per_batch.sum()
+    return per_batch
+
+
 # ------------------------------------------------------------------ bf16 path
 # Mixed-precision entry points (include/cfsd.h "bf16 path"): activations /
 # gradients are float32 or bfloat16 tensors, weights are the fp32 master view

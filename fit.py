@@ -1,7 +1,9 @@
 """``python fit.py --config C --checkpoint-dir D --mesh scan.obj --landmarks
-lm.json --template-landmarks idx.json --z-stats z_stats.pt --out PREFIX``: fit
-a trained model to an unregistered scan (the reference's Tester.fit_mesh,
-test.py:336-520) on the MI355X path (craniofacialsd-vae_amd/fitting.py)."""
+lm.json --template-landmarks idx.json --z-stats z_stats.pt --out PREFIX
+[--surface]``: fit a trained model to an unregistered scan (the reference's
+Tester.fit_mesh, test.py:336-520) on the MI355X path
+(craniofacialsd-vae_amd/fitting.py); ``--surface`` fits to the scan's
+triangles instead of its vertices and reports the surface error."""
 import os
 import sys
 

@@ -643,6 +643,57 @@ int cfsd_chamfer_bwd(const float* x, const float* y, const int32_t* idx_xy, cons
                      const int32_t* seg_j, const float* wx, const float* wy, float* gx, int batch, int by,
                      int n, int p, void* stream);
 
+/* ---------------------------------------------------------------- surface fitting
+ * Distance of points to a triangle mesh (Tester._point_mesh_distance,
+ * test.py:522-533: pytorch3d's point_face_distance), ABI 4.14.
+ *
+ * cfsd_point_face: points [bp, n, 3], verts [bv, nv, 3] fp32, faces [nf, 3]
+ * int32 shared by the batch; bp and bv are each 1 or `batch` (1 = shared, read
+ * in place).  Per point (b, i), over the CLOSED triangles of mesh b:
+ *   dist2[b, i]    = min_f |p - c_f|^2, c_f the nearest point of face f,
+ *   face_idx[b, i] = the arg min (int32; equal distances: the lowest f),
+ *   bary[b, i, 0:3] = the weights of c on the face's corners (sum 1).
+ * The distance is the difference form, built relative to the face's first
+ * corner; one instruction sequence per pair, so a pair gives the same bits
+ * wherever it is evaluated.  A zero-area face counts as its segment or point;
+ * finite input gives finite output.  Face indices read from memory are
+ * clamped into [0, nv).
+ *
+ * workspace: cfsd_point_face_workspace(bv, nf) bytes, 16-byte aligned, ALWAYS
+ * needed: a pre-launch writes 64 bytes per face (corners, bounding sphere)
+ * and one bounding sphere per CFSD_PF_GROUP consecutive faces there.  flags:
+ *   CFSD_PF_CULL      skip groups and faces whose sphere no lane of the wave
+ *                     can reach (exact: bit-identical to flags without it);
+ *   CFSD_PF_PREPARED  the workspace already holds THIS mesh's records (an
+ *                     earlier call with the same verts / faces): no pre-launch.
+ * seed_face [batch, n] int32 (may be NULL): per point one face whose distance
+ * bounds the search from the start, e.g. a face at the nearest referenced
+ * vertex; any face in range is valid (clamped), it only culls.
+ * stats [batch * ceil(n / 64), 2] int32 (may be NULL): per wave the groups
+ * entered and the faces evaluated. */
+#define CFSD_PF_GROUP 16
+#define CFSD_PF_CULL 1
+#define CFSD_PF_PREPARED 2
+size_t cfsd_point_face_workspace(int bv, int nf);
+int cfsd_point_face(const float* points, const float* verts, const int32_t* faces,
+                    const int32_t* seed_face, float* dist2, int32_t* face_idx, float* bary,
+                    int32_t* stats, void* workspace, size_t workspace_bytes, int batch, int bp, int bv,
+                    int n, int nv, int nf, int flags, void* stream);
+
+/* Gradient of sum_{b,i} g[b,i] dist2[b,i] through fixed faces and weights:
+ *   gp[b, i] = g[b,i] 2 (p - c)                    [batch, n, 3], always written
+ *   gv[b, u] = - sum_{(i,k): faces[face_idx[b,i], k] = u} gp[b, i] bary[b, i, k]
+ * gv [batch, nv, 3] may be NULL (points only).  The (point, corner) pairs are
+ * passed GROUPED by vertex: seg_e [batch, 3 n] = the pair numbers i * 3 + k of
+ * batch b ordered by (vertex, pair) (a stable sort), seg_ptr [batch, nv + 1]
+ * the offsets of each vertex's run.  One thread per vertex sums its run in
+ * ascending order: deterministic, no atomics; an empty run gives zero.  With
+ * bp = 1 or bv = 1 the caller sums gp or gv over the batch. */
+int cfsd_point_face_bwd(const float* points, const float* verts, const int32_t* faces,
+                        const int32_t* face_idx, const float* bary, const float* g, float* gp,
+                        const int32_t* seg_ptr, const int32_t* seg_e, float* gv, int batch, int bp,
+                        int bv, int n, int nv, int nf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,27 @@ back-to-back calls after ``--warmup`` calls:
   starts, total time / iterations (the closing error evaluation included);
 * ``decode_fwd_bwd_us``: the decoder forward + data-gradient backward alone
   (what an iteration spends outside the Chamfer search and Adam).
+
+``--surface`` measures the point-to-triangle search instead (the line kept as
+``profiles/fit_surface_bench.json``): the scan is demo mesh 5 with its
+vertices permuted and the template's faces re-indexed (P = 17 039 vertices,
+33 737 triangles), the generated side the same 16 decoded heads:
+
+* ``pf_gen_to_scan_{cull,brute}_us`` / ``pf_scan_to_gen_{cull,brute}_us``: one
+  ``ops.point_face_distance`` call per direction with culling on and off (the
+  culled call includes its seed: the gather of the referenced vertices and
+  ``ops.nn_points`` over them, timed alone as ``seed_*_us``; towards the scan
+  the per-face records are kept in an ``ops.SurfaceMesh``, towards the heads
+  every call includes the pre-launch that writes them); the scan's vertices
+  query in the Morton order of ``SurfaceMesh.queries``, as the fit uses them,
+  and ``scan_file_order_to_gen`` repeats the culled search in the permuted
+  file order (a wave's 64 queries are then scattered over the head);
+* ``groups_entered_*`` / ``faces_evaluated_*``: of the culled search, the
+  share of (wave, group) and (wave, face) pairs that pass the sphere tests;
+* ``pairs_per_us_*_brute``: point-triangle pairs per microsecond of the
+  brute-force walk (every pair evaluated: the price of one full test);
+* ``surface_fit_iteration_us`` and ``vertex_fit_iteration_us``: one iteration
+  of ``fitting.fit_points`` with and without the faces, in this process.
 """
 import argparse
 import json
@@ -48,6 +69,66 @@ def timed(fn, iters, warmup):
     return e0.elapsed_time(e1) * 1e3 / iters  # us
 
 
+def surface_main(opts, net, mean, std, x, dev):
+    """The ``--surface`` line (see the module docstring)."""
+    import numpy as np
+    import torch
+
+    import recipe
+    from craniofacialsd_vae_amd import fitting, ops
+
+    bsz, nv = x.shape[0], x.shape[1]
+    g = torch.Generator().manual_seed(2)
+    gf = torch.from_numpy(np.asarray(recipe.load_topology()["face_0"], np.int32).reshape(-1, 3)).to(dev)
+    full = torch.from_numpy(recipe.load_meshes()["verts"][5].astype(np.float32)).to(dev)
+    perm = torch.randperm(nv, generator=g).to(dev)  # scan vertex j = demo vertex perm[j]
+    inv = torch.empty_like(perm)
+    inv[perm] = torch.arange(nv, device=dev)
+    scan, sf = full[perm].contiguous()[None], inv[gf.long()].to(torch.int32).contiguous()
+    lidx = recipe.sample_idx(nv, k=12, seed=3).tolist()
+    lnd = full[lidx].contiguous()
+    mesh = ops.SurfaceMesh(scan, sf)
+    nf, ngroups = int(gf.shape[0]), (int(gf.shape[0]) + ops.PF_GROUP - 1) // ops.PF_GROUP
+    out = {"starts": bsz, "points": nv, "faces": nf, "iters": opts.iters, "brute_iters": opts.brute_iters}
+    gen_ref = ops.face_table(gf, nv).ref_idx
+    for key, pts, verts, faces in (("gen_to_scan", x, mesh, None), ("scan_to_gen", mesh.queries, x, gf),
+                                   ("scan_file_order_to_gen", scan, x, gf)):
+        on = ops.point_face_distance(pts, verts, faces, cull=True, return_stats=True)
+        off = ops.point_face_distance(pts, verts, faces, cull=False)
+        if not all(torch.equal(a, b) for a, b in zip(on[:3], off)):
+            raise RuntimeError(f"{key}: the culled search differs from brute force")
+        waves = on[3].shape[0]
+        out[f"groups_entered_{key}"] = round(int(on[3][:, 0].sum()) / (waves * ngroups), 4)
+        out[f"faces_evaluated_{key}"] = round(int(on[3][:, 1].sum()) / (waves * nf), 4)
+        out[f"pf_{key}_cull_us"] = round(timed(lambda: ops.point_face_distance(pts, verts, faces), opts.iters,
+                                               opts.warmup), 1)
+        if key == "scan_file_order_to_gen":
+            continue
+        us = timed(lambda: ops.point_face_distance(pts, verts, faces, cull=False), opts.brute_iters, 1)
+        out[f"pf_{key}_brute_us"] = round(us, 1)
+        out[f"pairs_per_us_{key}_brute"] = round(float(bsz) * nv * nf / us, 1)
+        if faces is None:
+            seed = lambda: ops.nn_points(pts, mesh.ref)  # noqa: E731
+        else:
+            seed = lambda: ops.nn_points(pts, verts.index_select(1, gen_ref).contiguous())  # noqa: E731
+        out[f"seed_{key}_us"] = round(timed(seed, opts.iters, opts.warmup), 1)
+
+    def fit(**kw):
+        return fitting.fit_points(net.decode, scan[0], lnd, lidx, mean, std, torch.zeros(recipe.LATENT), n_starts=bsz,
+                                  iterations=opts.fit_iters, seed=1, **kw)
+
+    for _ in range(2):  # alternate the two loops: the second pass is the one kept
+        out["surface_fit_iteration_us"] = round(
+            timed(lambda: fit(target_faces=sf, template_faces=gf), 1, 1) / opts.fit_iters, 1)
+        out["vertex_fit_iteration_us"] = round(timed(fit, 1, 1) / opts.fit_iters, 1)
+    res = fit(target_faces=sf, template_faces=gf)
+    out["fit_iters"] = opts.fit_iters
+    out["surface_term_first_last"] = [float(res.chamfer_history[0]), float(res.chamfer_history[-1])]
+    out["surface_distance_best"] = float(res.surface_mm)
+    print(json.dumps(out))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--starts", type=int, default=16)
@@ -56,6 +137,8 @@ def main(argv=None):
     ap.add_argument("--fit-iters", type=int, default=50)
     ap.add_argument("--cdist-iters", type=int, default=5)
     ap.add_argument("--cdist-chunk", type=int, default=2)
+    ap.add_argument("--surface", action="store_true", help="measure the point-to-triangle search instead")
+    ap.add_argument("--brute-iters", type=int, default=3)
     opts = ap.parse_args(argv)
 
     import numpy as np
@@ -94,6 +177,8 @@ def main(argv=None):
     y = full[torch.randperm(nv, generator=g).to(dev)].contiguous()[None]
     lidx = recipe.sample_idx(nv, k=12, seed=3).tolist()
     lnd = full[lidx].contiguous()
+    if opts.surface:
+        return surface_main(opts, net, mean, std, x, dev)
 
     out = {"starts": bsz, "points": nv, "iters": opts.iters}
     pairs = float(bsz) * nv * nv
