@@ -112,6 +112,12 @@ SIGNATURES = {
     "cfsd_point_face_workspace": (_Z, [_I, _I]),
     "cfsd_point_face": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _I, _P]),
     "cfsd_point_face_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "cfsd_raster_workspace": (_Z, [_I, _I]),
+    "cfsd_vertex_normals": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "cfsd_render_vertices": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F,
+                                  _F, _P]),
+    "cfsd_rasterize": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P]),
+    "cfsd_interpolate_colors": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _P]),
 }
 
 

@@ -8,7 +8,8 @@ Differences by design (the reference's CPU loader and per-step host syncs are
 what the MI355X path removes): batches come from :class:`engine.ResidentData`
 (device-drawn epoch shuffle + on-device swap inside the step), the seven
 ``.item()`` per step become one device accumulator read per epoch, and the
-train step can be replayed from a hipGraph.  Rendering, TensorBoard images
+train step can be replayed from a hipGraph.  ``render`` / ``log_images`` draw
+with libcfsd's rasteriser (``rendering.py``) and write PNG files; TensorBoard
 and the sklearn classifiers are out of scope.
 """
 import json
@@ -311,6 +312,64 @@ class ModelManager:
     def compute_vertex_errors(self, out, gt):
         """model_manager.py:395-400 (on device)."""
         return ops.vertex_errors(out.contiguous(), gt.contiguous(), to_mm=self.to_mm_const)
+
+    # ------------------------------------------------------------ pictures
+    @property
+    def template_faces(self):
+        """The template's triangles as the int32 device tensor the renderer takes."""
+        if getattr(self, "_template_faces", None) is None:
+            self._template_faces = torch.as_tensor(np.asarray(self.template.faces, np.int64),
+                                                   dtype=torch.int32).to(self.device)
+        return self._template_faces
+
+    @torch.no_grad()
+    def render(self, batched_verts, vertex_errors=None, error_max_scale=None):
+        """``ModelManager.render`` (``model_manager.py:625-658``): the meshes
+        ``batched_verts`` ``[B, V, 3]`` (un-normalised) seen from ``dist=2.5,
+        elev=0, azim=15`` at 256 x 256, ``[B, 3, 256, 256]`` on the device.
+        Without ``vertex_errors``: grey 0.5, Gouraud-shaded under a point
+        light at (0, 0, 3).  With ``vertex_errors`` ``[B, V]``: their plasma
+        colours over ``[0, error_max_scale]``, unshaded."""
+        from . import rendering
+        verts = batched_verts.detach().to(self.device, torch.float32).contiguous()
+        if vertex_errors is None:
+            return rendering.render(verts, self.template_faces, shading="gouraud")
+        colors = rendering.errors_to_colors(vertex_errors.to(self.device), 0, error_max_scale)
+        return rendering.render(verts, self.template_faces, colors, shading="none")
+
+    @torch.no_grad()
+    def log_images(self, in_data, out_dir, epoch, normalization_dict=None, phase="train", error_max_scale=5):
+        """``ModelManager.log_images`` (``model_manager.py:594-614``) with a
+        directory in the writer's place: ground truth | reconstruction | error
+        map of every mesh of ``in_data`` (``.x`` or the tensor, ``[B, V, 3]``),
+        side by side, in a grid of ``batch_size`` columns (4 without
+        ``swap_features``), written to ``<out_dir>/<phase>_<epoch + 1:08d>.png``.
+        Returns the path."""
+        from . import rendering
+        x = (in_data.x if hasattr(in_data, "x") else in_data).to(self.device, torch.float32)
+        self.net.eval()  # as after the reference's validation pass: z = mu
+        out = self.forward(x)[0]
+        if self._normalized_data:
+            mean = normalization_dict["mean"].to(self.device, torch.float32)
+            std = normalization_dict["std"].to(self.device, torch.float32)
+            x, out = x * std + mean, out * std + mean
+        errors = self.compute_vertex_errors(out, x)
+        log = torch.cat([self.render(x), self.render(out), self.render(out, errors, error_max_scale)], dim=-1)
+        grid = rendering.make_grid(log, nrow=self.bs if self._swap_features else 4, padding=10, pad_value=1.0)
+        os.makedirs(out_dir, exist_ok=True)
+        return rendering.save_png(os.path.join(out_dir, f"{phase}_{epoch + 1:08d}.png"), grid)
+
+    def visualization_batch(self, data):
+        """The meshes :meth:`log_images` draws for a resident set: its first
+        ``batch_size`` meshes and, with ``swap_features``, their ``bs x bs``
+        swap on region 0 (the reference keeps the first batch of each loader,
+        train.py:45-46)."""
+        idx = data.rows[:self.bs] if data.rows is not None else torch.arange(self.bs, device=self.device)
+        idx = idx.to(torch.int32).contiguous()
+        if not self._swap_features:
+            return data.meshes.index_select(0, idx.long())
+        key = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return ops.swap_features(data.meshes, idx, self.topology.region_mask, key, self.bs)
 
     def save_weights(self, checkpoint_dir, epoch):
         return self.engine.save_weights(checkpoint_dir, epoch)

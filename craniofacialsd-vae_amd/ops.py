@@ -1267,6 +1267,181 @@ def surface_distance(gen_verts, gen_faces, scan_verts, scan_faces=None, batch_re
     return per_batch
 
 
+# ------------------------------------------------------------------ rendering
+RN_GROUP = 16        # CFSD_RN_GROUP: faces per group box of cfsd_rasterize (include/cfsd.h)
+RN_MAX_SIZE = 4096   # CFSD_RN_MAX_SIZE: largest image side
+
+
+class RenderFaces:
+    """A face tensor prepared for rendering: its :class:`FaceTable` and the
+    vertex -> faces runs of the normals (``vf_ptr`` ``[V + 1]``, ``vf_idx``
+    ``[3 F]`` int32: the face of every corner grouped by vertex, ascending, so
+    a vertex's normal is summed in one fixed order).  Built by
+    :func:`render_faces`."""
+
+    def __init__(self, table):
+        faces, nv = table.faces, table.n_verts
+        keys, order = torch.sort(faces.reshape(-1), stable=True)  # corner e = f * 3 + k: ascending f within a vertex
+        bounds = torch.arange(nv + 1, dtype=torch.int32, device=faces.device)
+        self.table = table
+        self.faces, self.n_verts, self.n_faces = faces, nv, table.n_faces
+        self.vf_ptr = torch.searchsorted(keys, bounds, out_int32=True).contiguous()
+        self.vf_idx = (order // 3).to(torch.int32).contiguous()
+
+
+_RENDER_FACES = {}  # id(FaceTable) -> RenderFaces (holds the table: the key stays its own)
+
+
+def render_faces(faces, n_verts):
+    """The :class:`RenderFaces` of ``faces`` (validated and cached the way
+    :func:`face_table` caches its tables)."""
+    if isinstance(faces, RenderFaces):
+        if faces.n_verts != n_verts:
+            raise ValueError(f"faces: prepared for {faces.n_verts} vertices, mesh has {n_verts}")
+        return faces
+    tab = face_table(faces, n_verts)
+    rf = _RENDER_FACES.pop(id(tab), None)
+    if rf is None or rf.table is not tab:
+        rf = RenderFaces(tab)
+    _RENDER_FACES[id(tab)] = rf
+    while len(_RENDER_FACES) > 8:
+        _RENDER_FACES.pop(next(iter(_RENDER_FACES)))
+    return rf
+
+
+def _image_size(image_size):
+    s = int(image_size)
+    if s != image_size or s < 1 or s > RN_MAX_SIZE:
+        raise ValueError(f"image_size {image_size!r}: an integer in [1, {RN_MAX_SIZE}] expected")
+    return s
+
+
+def _rgb(value, name="background"):
+    """A colour given as one number or three."""
+    try:
+        v = [float(value)] * 3
+    except TypeError:
+        v = [float(c) for c in value]
+    if len(v) != 3:
+        raise ValueError(f"{name}: one value or three expected")
+    return v
+
+
+def _vertex_colors(colors, bsz, nv, device):
+    _need(colors, None, name="colors")
+    if colors.dim() != 3 or colors.shape[0] not in (1, bsz) or tuple(colors.shape[1:]) != (nv, 3):
+        raise ValueError(f"colors: shape {tuple(colors.shape)}, expected [{bsz} or 1, {nv}, 3]")
+    if colors.device != device:
+        raise ValueError("colors must be on the meshes' device")
+    return int(colors.shape[0])
+
+
+def vertex_normals(verts, faces):
+    """Area-weighted vertex normals ``[B, V, 3]`` of ``verts`` ``[B, V, 3]``
+    with ``faces`` ``[F, 3]`` (int32, shared by the batch): the normalised sum
+    of the un-normalised face normals at each vertex, zero for a vertex no
+    face uses (``cfsd_vertex_normals``)."""
+    bsz, nv = _points(verts, "verts")
+    rf = render_faces(faces, nv)
+    out = torch.empty_like(verts)
+    call("cfsd_vertex_normals", ptr(verts), ptr(rf.faces), ptr(rf.vf_ptr), ptr(rf.vf_idx), ptr(out), bsz, nv,
+         rf.n_faces, stream_ptr())
+    return out
+
+
+def project_vertices(verts, camera, faces=None, tex=None, light=(0.0, 0.0, 3.0), ambient=0.5, diffuse=1.0,
+                     specular=0.2, shininess=0.5, tex_value=0.5, shade=False):
+    """View transform and projection of ``verts`` ``[B, V, 3]`` by ``camera``
+    (a :class:`rendering.Camera`): ``(ndc_xy [B, V, 2], view_z [B, V])`` and,
+    with ``shade``, the Gouraud vertex colours ``[B, V, 3]`` (else None):
+    ``(ambient + diffuse max(n.L, 0)) tex + specular spec`` with ``tex`` ``[B
+    or 1, V, 3]`` or the constant ``tex_value`` (``cfsd_render_vertices``)."""
+    bsz, nv = _points(verts, "verts")
+    dev = verts.device
+    ndc = torch.empty((bsz, nv, 2), dtype=torch.float32, device=dev)
+    vz = torch.empty((bsz, nv), dtype=torch.float32, device=dev)
+    colors = fp = vp = vi = None
+    bt, nf = 1, 1
+    if shade:
+        rf = render_faces(faces, nv)
+        fp, vp, vi, nf = rf.faces, rf.vf_ptr, rf.vf_idx, rf.n_faces
+        if tex is not None:
+            bt = _vertex_colors(tex, bsz, nv, dev)
+        colors = torch.empty((bsz, nv, 3), dtype=torch.float32, device=dev)
+    lx, ly, lz = (float(c) for c in light)
+    call("cfsd_render_vertices", ptr(verts), ptr(camera.tensor(dev)), ptr(fp), ptr(vp), ptr(vi), ptr(tex), ptr(ndc),
+         ptr(vz), ptr(colors), bsz, bt, nv, nf, lx, ly, lz, float(ambient), float(diffuse), float(specular),
+         float(shininess), float(tex_value), stream_ptr())
+    return ndc, vz, colors
+
+
+def rasterize_ndc(ndc_xy, view_z, faces, image_size, znear=1.0, colors=None, background=0.0):
+    """The raster stage on projected vertices (``cfsd_rasterize``): ``ndc_xy``
+    ``[B, V, 2]``, ``view_z`` ``[B, V]``, ``faces`` ``[F, 3]`` int32 shared by
+    the batch.  Returns ``(pix_to_face [B, S, S] int32, zbuf [B, S, S], bary
+    [B, S, S, 3])`` with -1 on background pixels; with ``colors`` ``[B or 1,
+    V, 3]`` also the interpolated image ``[B, 3, S, S]`` over ``background``
+    (written by the same launch).  A face with a vertex at ``view_z <= znear``
+    is dropped."""
+    _need(ndc_xy, None, name="ndc_xy")
+    if ndc_xy.dim() != 3 or ndc_xy.shape[-1] != 2 or ndc_xy.shape[0] < 1 or ndc_xy.shape[1] < 1:
+        raise ValueError(f"ndc_xy: shape {tuple(ndc_xy.shape)}, expected [B, V >= 1, 2]")
+    bsz, nv = int(ndc_xy.shape[0]), int(ndc_xy.shape[1])
+    _need(view_z, (bsz, nv), name="view_z")
+    if view_z.device != ndc_xy.device:
+        raise ValueError("ndc_xy and view_z must be on one device")
+    tab = face_table(faces.table if isinstance(faces, RenderFaces) else faces, nv)
+    size, dev = _image_size(image_size), ndc_xy.device
+    bc, image = 1, None
+    if colors is not None:
+        bc = _vertex_colors(colors, bsz, nv, dev)
+        image = torch.empty((bsz, 3, size, size), dtype=torch.float32, device=dev)
+    bg = _rgb(background)
+    if bsz * size * size * 3 >= 2 ** 31:
+        raise ValueError("rasterize: batch x pixels x 3 must stay below 2^31")
+    pix_to_face = torch.empty((bsz, size, size), dtype=torch.int32, device=dev)
+    zbuf = torch.empty((bsz, size, size), dtype=torch.float32, device=dev)
+    bary = torch.empty((bsz, size, size, 3), dtype=torch.float32, device=dev)
+    need = int(_abi.lib().cfsd_raster_workspace(bsz, tab.n_faces))
+    workspace = torch.empty(need // 4, dtype=torch.float32, device=dev)
+    call("cfsd_rasterize", ptr(ndc_xy), ptr(view_z), ptr(tab.faces), ptr(colors), ptr(pix_to_face), ptr(zbuf),
+         ptr(bary), ptr(image), ptr(workspace), need, bsz, bc, nv, tab.n_faces, size, float(znear), bg[0], bg[1],
+         bg[2], stream_ptr())
+    return (pix_to_face, zbuf, bary) if colors is None else (pix_to_face, zbuf, bary, image)
+
+
+def rasterize_meshes(verts, faces, camera, image_size):
+    """``verts`` ``[B, V, 3]`` seen by ``camera`` (a
+    :class:`rendering.Camera`): ``(pix_to_face, zbuf, bary)`` as
+    :func:`rasterize_ndc` returns them."""
+    _points(verts, "verts")
+    _image_size(image_size)
+    ndc, vz, _ = project_vertices(verts, camera)
+    return rasterize_ndc(ndc, vz, faces, image_size, znear=camera.znear)
+
+
+def interpolate_vertex_colors(pix_to_face, bary, faces, colors, background=0.0):
+    """The image ``[B, 3, S, S]`` of a finished raster stage: per covered
+    pixel the ``bary`` mix of the winning face's vertex colours (``colors``
+    ``[B or 1, V, 3]``), ``background`` elsewhere (``cfsd_interpolate_colors``)."""
+    _need(pix_to_face, None, torch.int32, "pix_to_face")
+    if pix_to_face.dim() != 3 or pix_to_face.shape[1] != pix_to_face.shape[2] or pix_to_face.shape[0] < 1:
+        raise ValueError(f"pix_to_face: shape {tuple(pix_to_face.shape)}, expected [B, S, S]")
+    bsz, size = int(pix_to_face.shape[0]), _image_size(pix_to_face.shape[1])
+    _need(bary, (bsz, size, size, 3), name="bary")
+    _need(colors, None, name="colors")
+    if colors.dim() != 3:
+        raise ValueError(f"colors: shape {tuple(colors.shape)}, expected [B or 1, V, 3]")
+    nv, dev = int(colors.shape[1]), pix_to_face.device
+    bc = _vertex_colors(colors, bsz, nv, dev)
+    tab = face_table(faces.table if isinstance(faces, RenderFaces) else faces, nv)
+    bg = _rgb(background)
+    image = torch.empty((bsz, 3, size, size), dtype=torch.float32, device=dev)
+    call("cfsd_interpolate_colors", ptr(pix_to_face), ptr(bary), ptr(tab.faces), ptr(colors), ptr(image), bsz, bc, nv,
+         tab.n_faces, size, bg[0], bg[1], bg[2], stream_ptr())
+    return image
+
+
 # ------------------------------------------------------------------ bf16 path
 # Mixed-precision entry points (include/cfsd.h "bf16 path"): activations /
 # gradients are float32 or bfloat16 tensors, weights are the fp32 master view

@@ -12,8 +12,11 @@ per-epoch loss means logged (model_manager.py:575-592; JSON lines under
 ``<output>/logs``), checkpoints every ``logging_frequency.save_weights``
 epochs in the reference's ``model_%08d.pt`` / ``optimizer.pt`` format.  At the
 end the latent statistics of the training set (test.py:95-117) are saved.
-Rendering (tb_renderings), latent traversal videos and the classifiers are
-out of scope.
+With ``--renderings`` the lead rank also writes, every
+``logging_frequency.tb_renderings`` epochs, a ground truth | reconstruction |
+error map picture of one training and one validation batch
+(model_manager.py:594-614, train.py:66-70) into ``<output>/renderings``.
+Latent traversal videos and the classifiers are out of scope.
 """
 import argparse
 import os
@@ -33,6 +36,8 @@ def main(argv=None):
     parser.add_argument("--no-graph", action="store_true", help="eager launches (no hipGraph replay)")
     parser.add_argument("--epochs", type=int, default=None, help="override optimization.epochs")
     parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--renderings", action="store_true",
+                        help="write pictures every logging_frequency.tb_renderings epochs")
     opts = parser.parse_args(argv)
 
     import torch
@@ -78,6 +83,8 @@ def main(argv=None):
     start_epoch = manager.resume(checkpoint_dir) if opts.resume else 0
     epochs = opts.epochs if opts.epochs is not None else config["optimization"]["epochs"]
     save_every = config.get("logging_frequency", {}).get("save_weights", 100)
+    render_every = config.get("logging_frequency", {}).get("tb_renderings", 50) if opts.renderings else 0
+    render_dir = os.path.join(output_directory, "renderings")
     history = []
     for epoch in range(start_epoch, epochs):
         t0 = time.perf_counter()
@@ -91,6 +98,11 @@ def main(argv=None):
                 manager.log_losses(writer, epoch, "validation", va)
             print(f"epoch {epoch + 1}: train tot {tr['tot']:.5f}"
                   + (f", validation tot {va['tot']:.5f}" if va else ""), flush=True)
+            if render_every and (epoch + 1) % render_every == 0:
+                for phase, dset in (("train", train_set), ("validation", val_set)):
+                    if dset is not None:
+                        manager.log_images(manager.visualization_batch(dset), render_dir, epoch, norm, phase,
+                                           error_max_scale=2)
             if (epoch + 1) % save_every == 0:
                 manager.save_weights(checkpoint_dir, epoch)
     # latent statistics of the training set (Tester.compute_latent_stats)

@@ -694,6 +694,71 @@ int cfsd_point_face_bwd(const float* points, const float* verts, const int32_t* 
                         const int32_t* seg_ptr, const int32_t* seg_e, float* gv, int batch, int bp,
                         int bv, int n, int nv, int nf, void* stream);
 
+/* ---------------------------------------------------------------- rendering
+ * The pictures of ModelManager.render / log_images (model_manager.py:594-658:
+ * pytorch3d's MeshRasterizer with HardGouraudShader / ShadelessShader), ABI
+ * 4.15.  A deterministic z-buffer rasteriser: no atomics, two calls give the
+ * same bits, a mesh gives the same bits alone or in a batch.  verts
+ * [batch, nv, 3] fp32, faces [nf, 3] int32 shared by the batch (indices read
+ * from memory are clamped into [0, nv)).
+ *
+ * Convention.  cam: 14 device floats, R [3, 3] row-major, T [3], s = 1 /
+ * tan(fov / 2), znear; X_view = X R + T (row vectors), x_ndc = s x_view /
+ * z_view, y_ndc = s y_view / z_view.  NDC +X points left and +Y up: pixel
+ * (row i, column j) of an S x S image has its centre at x = 1 - (2j + 1) / S,
+ * y = 1 - (2i + 1) / S.  A pixel is covered by a face when the three edge
+ * functions of the projected triangle at the pixel centre have the sign of
+ * its area or are zero (inclusive edges); no back-face culling; a face of zero
+ * projected area covers nothing; a face with any vertex at z_view <= znear is
+ * dropped whole (no clipping).  Barycentrics are perspective-correct,
+ * w_i' = (w_i / z_i) / sum_k (w_k / z_k), z = 1 / sum_k (w_k / z_k); the nearest
+ * z wins, bit-equal z: the lowest face.
+ *
+ * cfsd_vertex_normals: normals [batch, nv, 3] = the normalised sum over the
+ * faces at a vertex of cross(v1 - v0, v2 - v0) (area weighting), 0 for a
+ * vertex without a face or with a zero sum.  The faces of vertex v are
+ * vf_idx[vf_ptr[v] .. vf_ptr[v + 1]) (vf_ptr [nv + 1], vf_idx [3 nf], int32:
+ * the face of every corner, grouped by vertex, ascending), summed in that
+ * order by one thread.
+ *
+ * cfsd_render_vertices: ndc [batch, nv, 2] and vz [batch, nv] (view z) of
+ * every vertex.  With colors [batch, nv, 3] != NULL also the Gouraud vertex
+ * colour in world space, n the vertex normal, C = -T R^T the camera centre:
+ *   L = normalize(light - p), V = normalize(C - p), d = max(n.L, 0),
+ *   r = 2 (n.L) n - L, spec = n.L > 0 ? max(r.V, 0)^shininess : 0,
+ *   colour = (ambient + diffuse d) tex + specular spec,
+ * tex [bt, nv, 3] (bt = 1 or batch) or, with tex = NULL, the constant
+ * tex_value.  faces, vf_ptr, vf_idx are needed only with colors.
+ *
+ * cfsd_rasterize: ndc, vz as written above (or any projected vertices).
+ *   pix_to_face [batch, S, S] int32, -1 = background,
+ *   zbuf [batch, S, S], bary [batch, S, S, 3] fp32, -1 = background,
+ * and, with colors [bc, nv, 3] (bc = 1 or batch) and image both != NULL,
+ *   image [batch, 3, S, S] = the bary mix of the winning face's vertex colours,
+ *   background pixels exactly (bg_r, bg_g, bg_b); nothing is clamped.
+ * workspace: cfsd_raster_workspace(batch, nf) bytes, 16-byte aligned: a
+ * pre-launch writes a 48-byte record per face and a pixel bounding box per
+ * CFSD_RN_GROUP consecutive faces there.  1 <= S <= CFSD_RN_MAX_SIZE.
+ *
+ * cfsd_interpolate_colors: the same image from a finished raster stage. */
+#define CFSD_RN_GROUP 16
+#define CFSD_RN_MAX_SIZE 4096
+size_t cfsd_raster_workspace(int batch, int nf);
+int cfsd_vertex_normals(const float* verts, const int32_t* faces, const int32_t* vf_ptr,
+                        const int32_t* vf_idx, float* normals, int batch, int nv, int nf, void* stream);
+int cfsd_render_vertices(const float* verts, const float* cam, const int32_t* faces,
+                         const int32_t* vf_ptr, const int32_t* vf_idx, const float* tex, float* ndc,
+                         float* vz, float* colors, int batch, int bt, int nv, int nf, float light_x,
+                         float light_y, float light_z, float ambient, float diffuse, float specular,
+                         float shininess, float tex_value, void* stream);
+int cfsd_rasterize(const float* ndc, const float* vz, const int32_t* faces, const float* colors,
+                   int32_t* pix_to_face, float* zbuf, float* bary, float* image, void* workspace,
+                   size_t workspace_bytes, int batch, int bc, int nv, int nf, int image_size, float znear,
+                   float bg_r, float bg_g, float bg_b, void* stream);
+int cfsd_interpolate_colors(const int32_t* pix_to_face, const float* bary, const int32_t* faces,
+                            const float* colors, float* image, int batch, int bc, int nv, int nf,
+                            int image_size, float bg_r, float bg_g, float bg_b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
