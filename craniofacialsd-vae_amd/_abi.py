@@ -118,6 +118,13 @@ SIGNATURES = {
                                   _F, _P]),
     "cfsd_rasterize": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P]),
     "cfsd_interpolate_colors": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _P]),
+    "cfsd_class_stats_workspace": (_Z, [_I, _I, _I]),
+    "cfsd_class_stats": (_I, [_P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P]),
+    "cfsd_discriminant_scores": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "cfsd_mlp_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
+    "cfsd_mlp_workspace": (_Z, [_P, _I, _I]),
+    "cfsd_mlp_train_steps": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F,
+                                  _F, _F, _P]),
 }
 
 

@@ -242,6 +242,8 @@ def fit_main(argv=None):
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--surface", action="store_true",
                         help="fit to the scan's triangles (its f lines), not its vertices")
+    parser.add_argument("--classifiers", default=None, metavar="CHECKPOINT_DIR",
+                        help="folder holding the classifier files of train.py: also report the fit's class")
     opts = parser.parse_args(argv)
 
     from . import data as D
@@ -274,5 +276,14 @@ def fit_main(argv=None):
             "landmark_mm": float(res.errors_lnd[res.best]), "z": res.z.cpu().tolist()}
     if opts.surface:
         line["surface_mm"] = float(res.surface_mm)
+    if opts.classifiers:  # test.py:446-451: encode the best fit, classify its latent with the QDA
+        manager.resume_classifiers(opts.classifiers)
+        v = res.verts.to(manager.device, torch.float32)
+        if norm is not None:
+            v = (v - norm["mean"].to(v.device)) / norm["std"].to(v.device)
+        z_p = manager.encode(v.unsqueeze(0).contiguous())
+        line["class_enc"] = manager.classify_latent(z_p, "qda")[0]
+        if "n" in manager.class2idx_dict:
+            line["maha_n"] = float(manager.mahalanobis_dist_to_qda_distribution(z_p, "n")[0])
     print(json.dumps(line))
     return line

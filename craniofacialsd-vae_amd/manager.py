@@ -9,8 +9,11 @@ what the MI355X path removes): batches come from :class:`engine.ResidentData`
 (device-drawn epoch shuffle + on-device swap inside the step), the seven
 ``.item()`` per step become one device accumulator read per epoch, and the
 train step can be replayed from a hipGraph.  ``render`` / ``log_images`` draw
-with libcfsd's rasteriser (``rendering.py``) and write PNG files; TensorBoard
-and the sklearn classifiers are out of scope.
+with libcfsd's rasteriser (``rendering.py``) and write PNG files.  With a
+``classifier:`` section the manager also carries the classifier stage
+(``classify.ClassifierStage``: MLP, LDA, QDA and the region LDAs / QDAs,
+``model_manager.py:403-573``) on libcfsd kernels; TensorBoard and the
+``LinearSVC`` are out of scope.
 """
 import json
 import os
@@ -20,6 +23,7 @@ import torch
 
 from . import engine as E
 from . import ops, precompute, refcache, topology
+from .classify import ClassifierStage
 from .step import TrainStep
 
 LOSS_KEYS = ["reconstruction", "kl", "latent_consistency", "laplacian", "classification",
@@ -84,7 +88,7 @@ class JsonlWriter:
             f.write(json.dumps({"tag": tag, "value": float(value), "step": int(step)}) + "\n")
 
 
-class ModelManager:
+class ModelManager(ClassifierStage):
     def __init__(self, configurations, device="cuda", precomputed_storage_path="precomputed",
                  precision="fp32", seed=0, use_graph=True, averager=None):
         self._model_params = configurations["model"]
@@ -115,6 +119,7 @@ class ModelManager:
             swap_bs=self.bs, seed=seed, device=self.device, precision=precision,
             swap_features=self._swap_features)
         self._latent_regions = self._compute_latent_regions()
+        self._init_classifiers(configurations, seed)  # nothing without a classifier: section
         self._batch_diagonal_idx = [(self.bs + 1) * i for i in range(self.bs)]
         self._losses = None
         self.use_graph = use_graph
@@ -375,7 +380,13 @@ class ModelManager:
         return self.engine.save_weights(checkpoint_dir, epoch)
 
     def resume(self, checkpoint_dir):
-        return self.engine.resume(checkpoint_dir)
+        """``ModelManager.resume`` (``model_manager.py:690-706``): the last
+        model and the optimiser state; with a ``classifier:`` section also
+        whatever classifier files the folder holds."""
+        epoch = self.engine.resume(checkpoint_dir)
+        if self._classifier_params is not None:
+            self.resume_classifiers(checkpoint_dir)
+        return epoch
 
 
 def _engine_model(engine, arrays, model_params, device):

@@ -882,8 +882,149 @@ def reconstruction_error_stats(mesh_means):
             "max": torch.max(mesh_means).item(), "std": torch.std(mesh_means).item()}
 
 
+# ------------------------------------------------------------------ classifiers
+CLS_MAX_D = 128      # widest column window of cfsd_class_stats / cfsd_discriminant_scores
+CLS_MAX_CLASSES = 64
+MLP_MAX_LAYERS = 6
+MLP_MAX_WIDTH = 1024
+MLP_MAX_BS = 16
+
+
+def _window(z, cols, name="z"):
+    """``z`` [n, ld] and the column window ``cols = (col0, d)`` (default: all)."""
+    _need(z, None, name=name)
+    if z.dim() != 2 or z.shape[0] < 1:
+        raise ValueError(f"{name}: shape {tuple(z.shape)}, expected [N >= 1, D]")
+    n, ld = int(z.shape[0]), int(z.shape[1])
+    col0, d = (0, ld) if cols is None else (int(cols[0]), int(cols[1]))
+    if col0 < 0 or d < 1 or col0 + d > ld:
+        raise ValueError(f"columns [{col0}, {col0 + d}) outside [0, {ld})")
+    if d > CLS_MAX_D:
+        raise ValueError(f"{d} columns: at most {CLS_MAX_D} are supported")
+    return n, ld, col0, d
+
+
+def class_stats(z, label, n_classes, cols=None, workspace=None):
+    """Per-class count, mean and centred scatter (``cfsd_class_stats``) of the
+    columns ``cols = (col0, d)`` of ``z`` ``[n, ld]``; ``label`` ``[n]`` int32,
+    a label outside ``[0, n_classes)`` drops its row.  Returns ``(count [C]
+    int32, mean [C, d], scatter [C, d, d])`` on the device."""
+    n, ld, col0, d = _window(z, cols)
+    _need(label, (n,), torch.int32, "label")
+    if not 1 <= n_classes <= CLS_MAX_CLASSES:
+        raise ValueError(f"{n_classes} classes: 1..{CLS_MAX_CLASSES} are supported")
+    need = int(_abi.lib().cfsd_class_stats_workspace(n, d, n_classes))
+    workspace, nbytes = _conv_ws(workspace, z.device, need)
+    count = torch.empty((n_classes,), dtype=torch.int32, device=z.device)
+    mean = torch.empty((n_classes, d), dtype=torch.float32, device=z.device)
+    scatter = torch.empty((n_classes, d, d), dtype=torch.float32, device=z.device)
+    call("cfsd_class_stats", ptr(z), ptr(label), ptr(count), ptr(mean), ptr(scatter), ptr(workspace),
+         ctypes.c_size_t(nbytes), n, ld, col0, d, n_classes, stream_ptr())
+    return count, mean, scatter
+
+
+def discriminant_scores(z, mean, whiten, offset, cols=None, want_maha2=False, want_scores=True, want_pred=True):
+    """``cfsd_discriminant_scores``: per row of the column window of ``z`` and
+    class c, ``maha2 = |(z - mean_c) whiten_c|^2`` and ``scores = -0.5 maha2 +
+    offset_c``; ``pred`` the arg max (lowest class on ties).  ``whiten``
+    ``[C, d, d]`` (QDA) or ``[1, d, d]`` (shared, LDA).  Returns the dict of
+    the outputs asked for."""
+    n, ld, col0, d = _window(z, cols)
+    _need(mean, None, name="mean")
+    c = int(mean.shape[0])
+    _need(mean, (c, d), name="mean")
+    _need(offset, (c,), name="offset")
+    _need(whiten, None, name="whiten")
+    if whiten.dim() != 3 or whiten.shape[0] not in (1, c) or tuple(whiten.shape[1:]) != (d, d):
+        raise ValueError(f"whiten: shape {tuple(whiten.shape)}, expected [{c} or 1, {d}, {d}]")
+    if not 1 <= c <= CLS_MAX_CLASSES:
+        raise ValueError(f"{c} classes: 1..{CLS_MAX_CLASSES} are supported")
+    out = {}
+    if want_maha2:
+        out["maha2"] = torch.empty((n, c), dtype=torch.float32, device=z.device)
+    if want_scores:
+        out["scores"] = torch.empty((n, c), dtype=torch.float32, device=z.device)
+    if want_pred:
+        out["pred"] = torch.empty((n,), dtype=torch.int32, device=z.device)
+    call("cfsd_discriminant_scores", ptr(z), ptr(mean), ptr(whiten), ptr(offset), ptr(out.get("maha2")),
+         ptr(out.get("scores")), ptr(out.get("pred")), n, ld, col0, d, c, int(whiten.shape[0]), stream_ptr())
+    return out
+
+
+def mlp_dims(dims):
+    """The host width array of the MLP entry points, validated."""
+    dims = [int(v) for v in dims]
+    if not 2 <= len(dims) <= MLP_MAX_LAYERS + 1:
+        raise ValueError(f"{len(dims) - 1} layers: 1..{MLP_MAX_LAYERS} are supported")
+    if min(dims) < 1 or max(dims) > MLP_MAX_WIDTH:
+        raise ValueError(f"widths {dims}: 1..{MLP_MAX_WIDTH} are supported")
+    return dims, (ctypes.c_int * len(dims))(*dims)
+
+
+def mlp_param_count(dims):
+    return sum(dims[i + 1] * dims[i] + dims[i + 1] for i in range(len(dims) - 1))
+
+
+def mlp_forward(z, params, dims):
+    """The reference ``MLPClassifier`` (``model.py:191-203``: a ReLU after
+    every Linear, the last included) in one launch (``cfsd_mlp_fwd``):
+    ``z`` ``[n, dims[0]]``, ``params`` the flat fp32 buffer in ``state_dict``
+    order.  Returns ``(logits [n, dims[-1]], pred [n] int32)``."""
+    dims, cdims = mlp_dims(dims)
+    _need(z, None, name="z")
+    if z.dim() != 2 or z.shape[0] < 1 or z.shape[1] != dims[0]:
+        raise ValueError(f"z: shape {tuple(z.shape)}, expected [N >= 1, {dims[0]}]")
+    _need(params, (mlp_param_count(dims),), name="params")
+    n = int(z.shape[0])
+    logits = torch.empty((n, dims[-1]), dtype=torch.float32, device=z.device)
+    pred = torch.empty((n,), dtype=torch.int32, device=z.device)
+    call("cfsd_mlp_fwd", ptr(z), ptr(params), ptr(logits), ptr(pred), cdims, len(dims) - 1, n, stream_ptr())
+    return logits, pred
+
+
+def mlp_workspace(dims, bs):
+    dims, cdims = mlp_dims(dims)
+    return int(_abi.lib().cfsd_mlp_workspace(cdims, len(dims) - 1, int(bs)))
+
+
+def mlp_train_steps(z, label, class_weight, params, m, v, step, acc, dims, bs, n_steps, row0=0, train=True, lr=1e-4,
+                    beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, workspace=None, dw_out=None):
+    """``n_steps`` consecutive steps of ``mlp_classifier_epoch``
+    (``model_manager.py:428-446``) over the rows ``[row0 + t bs, +bs)`` of
+    ``z`` / ``label`` in ONE call (``cfsd_mlp_train_steps``: two launches per
+    step).  ``acc`` ``[3]`` gains ``{loss, acc, 1}`` per step; ``step`` (int32
+    device scalar) is Adam's t.  ``train=False`` is the validation epoch:
+    parameters, moments and ``step`` stay untouched."""
+    dims, cdims = mlp_dims(dims)
+    _need(z, None, name="z")
+    if z.dim() != 2 or z.shape[1] != dims[0]:
+        raise ValueError(f"z: shape {tuple(z.shape)}, expected [N, {dims[0]}]")
+    n_rows = int(z.shape[0])
+    _need(label, (n_rows,), torch.int32, "label")
+    _need(class_weight, (dims[-1],), name="class_weight")
+    if not 1 <= bs <= MLP_MAX_BS:
+        raise ValueError(f"batch size {bs}: 1..{MLP_MAX_BS} are supported")
+    if n_steps < 0 or row0 < 0 or row0 + n_steps * bs > n_rows:
+        raise ValueError(f"rows [{row0}, +{n_steps} x {bs}) outside [0, {n_rows})")
+    n = mlp_param_count(dims)
+    _need(params, (n,), name="params")
+    _need(acc, (3,), name="acc")
+    nbytes = 0
+    if train:
+        _need(m, (n,), name="m")
+        _need(v, (n,), name="v")
+        _need(step, (1,), torch.int32, "step")
+        workspace, nbytes = _conv_ws(workspace, z.device, mlp_workspace(dims, bs))
+    if dw_out is not None:
+        _need(dw_out, (n,), name="dw_out")
+    call("cfsd_mlp_train_steps", ptr(z), ptr(label), ptr(class_weight), ptr(params), ptr(m), ptr(v), ptr(step),
+         ptr(acc), ptr(workspace) if train else None, ctypes.c_size_t(nbytes), ptr(dw_out), cdims, len(dims) - 1,
+         n_rows, int(row0), int(bs), int(n_steps), int(bool(train)), float(lr), float(beta1), float(beta2),
+         float(eps), float(weight_decay), stream_ptr())
+
+
 # ------------------------------------------------------------------ latent fitting
-NN_TILE = 16  # CFSD_NN_TILE: reference points per chunk of cfsd_nn_points (include/cfsd.h)
+NN_TILE = 16 # CFSD_NN_TILE: reference points per chunk of cfsd_nn_points (include/cfsd.h)
 
 
 def _points(t, name):

@@ -16,9 +16,15 @@ With ``--renderings`` the lead rank also writes, every
 ``logging_frequency.tb_renderings`` epochs, a ground truth | reconstruction |
 error map picture of one training and one validation batch
 (model_manager.py:594-614, train.py:66-70) into ``<output>/renderings``.
-Latent traversal videos and the classifiers are out of scope.
+With a ``classifier:`` section in the configuration the lead rank then runs
+the classifier stage (train.py:76-77, model_manager.py:448-504): the MLP
+classifier, LDA, QDA and the region LDAs / QDAs on the eval-mode latents, their
+files written next to the checkpoints and the validation accuracies to
+``<output>/classifiers.json``.  Latent traversal videos and the ``LinearSVC``
+are out of scope.
 """
 import argparse
+import json
 import os
 import shutil
 import sys
@@ -110,6 +116,10 @@ def main(argv=None):
         z = manager.encode(train_set.meshes)
         stats = manager.engine.latent_stats(z)
         torch.save({k: v.cpu() for k, v in stats.items()}, os.path.join(output_directory, "z_stats.pt"))
+        if "classifier" in config:
+            acc = manager.train_and_validate_classifiers(train_set, val_set, writer, checkpoint_dir)
+            with open(os.path.join(output_directory, "classifiers.json"), "w") as f:
+                json.dump({"validation_accuracy": acc, "classes": manager.class2idx_dict}, f)
     if world > 1:
         DD.barrier()
         DD.destroy()

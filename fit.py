@@ -3,7 +3,9 @@ lm.json --template-landmarks idx.json --z-stats z_stats.pt --out PREFIX
 [--surface]``: fit a trained model to an unregistered scan (the reference's
 Tester.fit_mesh, test.py:336-520) on the MI355X path
 (craniofacialsd-vae_amd/fitting.py); ``--surface`` fits to the scan's
-triangles instead of its vertices and reports the surface error."""
+triangles instead of its vertices and reports the surface error;
+``--classifiers CHECKPOINT_DIR`` also reports the fit's QDA class and its
+Mahalanobis distance to the normal class."""
 import os
 import sys
 

@@ -759,6 +759,69 @@ int cfsd_interpolate_colors(const int32_t* pix_to_face, const float* bary, const
                             const float* colors, float* image, int batch, int bc, int nv, int nf,
                             int image_size, float bg_r, float bg_g, float bg_b, void* stream);
 
+/* ---------------------------------------------------------------- classifiers
+ * The classifier stage after the VAE (ModelManager.train_and_validate_classifiers,
+ * model_manager.py:428-573): LDA / QDA on the latent code and the MLP
+ * classifier (model.py:191-203), ABI 4.16.  No atomics; every reduction runs
+ * in an order fixed by the shapes, so two calls give the same bits.  Dependent
+ * phases are separate launches enqueued by the entry point (no grid-wide
+ * barrier).  In this section a workspace too small for the shapes is a bad
+ * argument: CFSD_EINVAL.
+ *
+ * cfsd_class_stats: z [n, ld] fp32, of which the columns [col0, col0 + d) are
+ * read (a window: the region classifiers read their slice of the one latent
+ * buffer in place); label [n] int32.  A row whose label lies outside
+ * [0, n_classes) contributes to nothing.  Two passes in fp32 (mean first):
+ *   count [C] int32, mean [C, d] (0 for an empty class),
+ *   scatter [C, d, d] = sum_{i: label_i = c} (z_i - mean_c)(z_i - mean_c)^T.
+ * d <= 128, n_classes <= 64.  workspace: cfsd_class_stats_workspace() bytes
+ * (per-slice partial sums, merged in ascending slice order).
+ *
+ * cfsd_discriminant_scores: z as above; mean [C, d]; whiten [Cw, d, d] with
+ * Cw = n_whiten = C (one per class: QDA) or 1 (shared: LDA); offset [C].
+ *   maha2 [n, C]  = |(z_i - mean_c) whiten_c|^2
+ *   scores [n, C] = -0.5 maha2 + offset_c
+ *   pred [n] int32 = argmax_c scores, the lowest c among equal scores
+ * (each output may be NULL).
+ *
+ * cfsd_mlp_fwd: the whole MLPClassifier in one launch over n rows of
+ * z [n, dims[0]]: n_layers <= 6 Linear layers, every width <= 1024, `dims`
+ * a HOST array of n_layers + 1 widths, a ReLU after EVERY layer, the last
+ * included (model.py:196-197), so logits >= 0.  params: one flat fp32 buffer
+ * in state_dict order, W_0 [dims[1], dims[0]], b_0, W_1, ...
+ *   logits [n, dims[n_layers]], pred [n] int32 (argmax, lowest index on ties;
+ *   may be NULL).
+ *
+ * cfsd_mlp_train_steps: n_steps consecutive steps of mlp_classifier_epoch
+ * (model_manager.py:428-446) over the rows [row0 + t bs, row0 + (t + 1) bs) of
+ * z [n_rows, dims[0]] / label [n_rows], bs <= 16; two launches per step:
+ *  1. one workgroup: forward; loss = sum_i w[y_i] (logsumexp(o_i) - o_i[y_i]) /
+ *     sum_i w[y_i] (CrossEntropyLoss(class_weight)), acc = 100 correct / bs;
+ *     acc[3] += {loss, acc, 1}; *step += 1; the activation gradients (ReLU' = 0
+ *     at 0), each layer's input and output gradient left in the workspace;
+ *  2. one thread per parameter: its gradient (<= 16 terms, ascending row) and
+ *     the cfsd_adam update in place (m, v sized like params; *step the
+ *     1-based step number).  dw_out (may be NULL, sized like params) receives
+ *     the last step's gradient.
+ * train == 0: launch 1 without gradients (the validation epoch); params, m,
+ * v, step untouched (m, v, step, workspace may be NULL).  Labels are clamped
+ * into range.  workspace: cfsd_mlp_workspace(dims, n_layers, bs) bytes. */
+size_t cfsd_class_stats_workspace(int n, int d, int n_classes);
+int cfsd_class_stats(const float* z, const int32_t* label, int32_t* count, float* mean, float* scatter,
+                     void* workspace, size_t workspace_bytes, int n, int ld, int col0, int d,
+                     int n_classes, void* stream);
+int cfsd_discriminant_scores(const float* z, const float* mean, const float* whiten, const float* offset,
+                             float* maha2, float* scores, int32_t* pred, int n, int ld, int col0, int d,
+                             int n_classes, int n_whiten, void* stream);
+int cfsd_mlp_fwd(const float* z, const float* params, float* logits, int32_t* pred, const int* dims,
+                 int n_layers, int n, void* stream);
+size_t cfsd_mlp_workspace(const int* dims, int n_layers, int bs);
+int cfsd_mlp_train_steps(const float* z, const int32_t* label, const float* class_weight, float* params,
+                         float* m, float* v, int32_t* step, float* acc, void* workspace,
+                         size_t workspace_bytes, float* dw_out, const int* dims, int n_layers, int n_rows,
+                         int row0, int bs, int n_steps, int train, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
