@@ -43,11 +43,15 @@ def pixel_centres(size):
     return c[None, :].repeat(size, 0), c[:, None].repeat(size, 1)  # px [i, j] = c[j], py [i, j] = c[i]
 
 
-def raster64(ndc, vz, faces, size, znear=ZNEAR):
+def raster64(ndc, vz, faces, size, znear=ZNEAR, crop=False):
     """ndc [V, 2], vz [V] float64, faces [F, 3].  Returns a dict: face [S, S]
     (-1 background), z, bary [S, S, 3], area [S, S] (the winner's triangle
-    area), ambiguous [S, S]."""
-    px, py = pixel_centres(size)
+    area), ambiguous [S, S], tie [S, S] (the two nearest depths are equal).
+    ``crop``: a face's pass visits only its pixel box grown by two pixels, not
+    the image; every pixel the face covers, or comes within the edge tolerance
+    of, lies inside it, so the result is the same (test_render_host.py shows
+    it)."""
+    gx, gy = pixel_centres(size)
     best = np.full((size, size), np.inf)
     second = np.full((size, size), np.inf)
     face = np.full((size, size), -1, np.int64)
@@ -55,6 +59,7 @@ def raster64(ndc, vz, faces, size, znear=ZNEAR):
     area = np.zeros((size, size))
     edge_amb = np.zeros((size, size), bool)
     tol = 1e-3 * 2.0 / size  # 1e-3 pixel in NDC units
+    whole = (slice(None), slice(None))
     for f, (i0, i1, i2) in enumerate(np.asarray(faces)):
         x, y, z = ndc[[i0, i1, i2], 0], ndc[[i0, i1, i2], 1], vz[[i0, i1, i2]]
         if (z <= znear).any():
@@ -62,6 +67,20 @@ def raster64(ndc, vz, faces, size, znear=ZNEAR):
         a = (x[1] - x[0]) * (y[2] - y[0]) - (y[1] - y[0]) * (x[2] - x[0])
         if a == 0.0:
             continue
+        box = whole
+        if crop:  # pixel j has its centre at 1 - (2j + 1) / S: j = ((1 - c) S - 1) / 2
+            j0, j1 = ((1.0 - x.max()) * size - 1.0) / 2, ((1.0 - x.min()) * size - 1.0) / 2
+            r0, r1 = ((1.0 - y.max()) * size - 1.0) / 2, ((1.0 - y.min()) * size - 1.0) / 2
+            if not all(map(np.isfinite, (j0, j1, r0, r1))):
+                raise ValueError("raster64(crop=True) needs finite coordinates")
+            if np.ceil(j0 - 0.01) > np.floor(j1 + 0.01) or np.ceil(r0 - 0.01) > np.floor(r1 + 0.01):
+                continue  # no pixel centre within 0.01 pixel (ten tolerances) of the face's box
+            j0, j1 = max(int(np.floor(j0)) - 2, 0), min(int(np.ceil(j1)) + 2, size - 1)
+            r0, r1 = max(int(np.floor(r0)) - 2, 0), min(int(np.ceil(r1)) + 2, size - 1)
+            if j0 > j1 or r0 > r1:
+                continue
+            box = (slice(r0, r1 + 1), slice(j0, j1 + 1))
+        px, py = gx[box], gy[box]
         sgn = 1.0 if a > 0 else -1.0
         w, dist = [], []
         for p, q in ((1, 2), (2, 0), (0, 1)):  # w_k: the edge opposite corner k
@@ -71,24 +90,25 @@ def raster64(ndc, vz, faces, size, znear=ZNEAR):
             dist.append(sgn * wk / ln if ln > 0 else np.full_like(wk, np.inf))
         dist = np.stack(dist)
         near = (dist >= -tol).all(0)  # the face grown by the tolerance contains the pixel
-        edge_amb |= near & (np.abs(dist) <= tol).any(0)
+        edge_amb[box] |= near & (np.abs(dist) <= tol).any(0)
         inside = (sgn * w[0] >= 0) & (sgn * w[1] >= 0) & (sgn * w[2] >= 0)
         if not inside.any():
             continue
         t = np.stack([w[k] / a / z[k] for k in range(3)], -1)
         with np.errstate(divide="ignore", invalid="ignore"):  # pixels off the face: unused values
             zz = 1.0 / t.sum(-1)
-            closer = inside & (zz < best)  # strict: equal depth keeps the lower face
-            second = np.where(closer, np.minimum(best, second), np.where(inside, np.minimum(second, zz), second))
-            bary = np.where(closer[..., None], t * zz[..., None], bary)
-        best = np.where(closer, zz, best)
-        face = np.where(closer, f, face)
-        area = np.where(closer, abs(a) / 2, area)
+            closer = inside & (zz < best[box])  # strict: equal depth keeps the lower face
+            second[box] = np.where(closer, np.minimum(best[box], second[box]),
+                                   np.where(inside, np.minimum(second[box], zz), second[box]))
+            bary[box] = np.where(closer[..., None], t * zz[..., None], bary[box])
+        best[box] = np.where(closer, zz, best[box])
+        face[box] = np.where(closer, f, face[box])
+        area[box] = np.where(closer, abs(a) / 2, area[box])
     hit = face >= 0
     with np.errstate(invalid="ignore"):
         depth_amb = hit & (second - best < 1e-4 * best)
     return {"face": face, "z": np.where(hit, best, -1.0), "bary": bary, "area": area,
-            "ambiguous": edge_amb | depth_amb}
+            "ambiguous": edge_amb | depth_amb, "tie": hit & (second == best)}
 
 
 def normals64(verts, faces):
@@ -211,15 +231,26 @@ def icosphere(levels=2):
 
 SCALES = [(0.9, 1.1, 0.8), (0.7, 0.8, 1.0), (1.0, 0.6, 0.9)]
 SHIFT = (0.03, -0.02, 0.01)
-SIZES = (64, 48)
+SIZES = (64, 48, 20, 44, 100)  # 20, 44, 100: partial tiles on the right and at the bottom
+_SCENE = {}
 
 
 @pytest.fixture(scope="module")
 def scene(mods):
+    return sphere_scene(mods[1])
+
+
+def sphere_scene(rendering):
     """The three spheres (float32 vertices; the last vertex belongs to no
     face), their device copies, and per image size the oracle of each mesh:
-    raster stage, Gouraud and shadeless images.  Computed once."""
-    _, rendering = mods
+    raster stage, Gouraud and shadeless images.  Computed once per process
+    (test_gpu_render_walk.py uses it too)."""
+    if not _SCENE:
+        _SCENE.update(_sphere_scene(rendering))
+    return _SCENE
+
+
+def _sphere_scene(rendering):
     v, faces = icosphere(2)
     assert faces.shape == (320, 3)
     v = np.concatenate([v, [[0.0, 0.0, 0.2]]])  # isolated
@@ -313,8 +344,12 @@ def test_vertex_normals_and_gouraud_colors(mods, scene):
 
 # ------------------------------------------------------------------ determinism
 def test_bits_do_not_depend_on_call_batch_or_face_order(mods, scene):
+    for size in (64, 44):  # whole tiles only, and partial ones on two sides
+        _bits_do_not_depend_on_call_batch_or_face_order(mods, scene, size)
+
+
+def _bits_do_not_depend_on_call_batch_or_face_order(mods, scene, size):
     ops, rendering = mods
-    size = 64
     dv, df, dc = scene["d_verts"], scene["d_faces"], scene["d_colors"]
 
     def run(verts, faces, colors):

@@ -260,3 +260,64 @@ def test_errors_to_colors_index_rule():
     np.testing.assert_array_equal(auto, tab[[0, 255, 128]])
     with pytest.raises(ValueError):
         rendering.errors_to_colors(e, 0, 1, cmap="viridis")
+
+
+# ------------------------------------------------------------------ the GPU suite's oracle and scenes
+def _same(a, b):
+    assert a.keys() == b.keys()
+    for k in a:
+        assert np.array_equal(a[k], b[k], equal_nan=True), k
+
+
+def _sphere_at_48():
+    from test_gpu_render import SCALES, SHIFT, icosphere
+    v, faces = icosphere(2)
+    v = (v * np.asarray(SCALES[0]) + np.asarray(SHIFT)).astype(np.float32).astype(np.float64)
+    ndc, vz = rendering.look_at().project(v)
+    return ndc, vz, faces
+
+
+def test_raster64_crop_changes_nothing():
+    """The oracle's per-face pass over the face's pixel box grown by two
+    pixels gives what the pass over the whole image gives, field by field."""
+    from test_gpu_render import exact_scene, raster64
+    ndc, vz, faces = exact_scene()
+    _same(raster64(ndc, vz, faces, 16), raster64(ndc, vz, faces, 16, crop=True))
+    ndc, vz, faces = _sphere_at_48()
+    whole = raster64(ndc, vz, faces, 48)
+    assert 0.2 < np.mean(whole["face"] >= 0) < 0.9 and whole["ambiguous"].any()
+    _same(whole, raster64(ndc, vz, faces, 48, crop=True))
+
+
+def test_torch_owner_search_is_raster64():
+    """The chunked torch restatement of the oracle (the real head's owner
+    search on the GPU) against raster64, on the CPU: the same owners, the
+    same ambiguity mask, the same depths; with a chunk that splits the list."""
+    from test_gpu_render import exact_scene, raster64
+    from test_gpu_render_walk import raster64_torch
+    for (ndc, vz, faces), size in ((exact_scene(), 16), (_sphere_at_48(), 48)):
+        ref = raster64(ndc, vz, faces, size)
+        for chunk in (7, 128):
+            got = raster64_torch(torch.from_numpy(ndc), torch.from_numpy(vz), torch.from_numpy(faces).long(), size,
+                                 chunk=chunk)
+            assert np.array_equal(got["face"].numpy(), ref["face"])
+            assert np.array_equal(got["ambiguous"].numpy(), ref["ambiguous"])
+            np.testing.assert_allclose(got["z"].numpy(), ref["z"], rtol=1e-14)
+
+
+def test_lattice_scene_is_exact_in_float32():
+    """The two-round lattice of test_gpu_render_walk.py: the float32
+    restatement of the kernel's arithmetic gives the float64 oracle's owners,
+    depths and weights at every pixel of both meshes at every size, bit for
+    bit, and the oracle shows what the scene is built to show."""
+    from test_gpu_render_walk import LATTICE_SIZES, check_lattice_facts, lattice_refs, raster_np
+    lat = lattice_refs()
+    check_lattice_facts(lat)
+    for size in LATTICE_SIZES:
+        for m in range(2):
+            ref = lat["ref"][size][m]
+            for dtype in (np.float32, np.float64):
+                got = raster_np(lat["ndc"], lat["vz"][m], lat["faces"], size, dtype)
+                assert np.array_equal(got["face"], ref["face"]), (size, m, dtype)
+                assert np.array_equal(got["z"].astype(np.float64), ref["z"])
+                assert np.array_equal(got["bary"].astype(np.float64), ref["bary"])
