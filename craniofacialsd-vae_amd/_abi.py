@@ -106,6 +106,8 @@ SIGNATURES = {
     "cfsd_scale": (_I, [_P, _Z, _F, _P]),
     "cfsd_elu_bwd": (_I, [_P, _P, _P, _Z, _P]),
     "cfsd_vertex_errors": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    "cfsd_group_vertex_errors": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "cfsd_region_means": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "cfsd_nn_points_workspace": (_Z, [_I, _I, _I]),
     "cfsd_nn_points": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P]),
     "cfsd_chamfer_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -13,7 +13,8 @@ with libcfsd's rasteriser (``rendering.py``) and write PNG files.  With a
 ``classifier:`` section the manager also carries the classifier stage
 (``classify.ClassifierStage``: MLP, LDA, QDA and the region LDAs / QDAs,
 ``model_manager.py:403-573``) on libcfsd kernels; TensorBoard and the
-``LinearSVC`` are out of scope.
+``LinearSVC`` are out of scope.  The reference's
+``Tester`` over a resumed manager is ``evaluation.Tester``.
 """
 import json
 import os
@@ -133,6 +134,10 @@ class ModelManager(ClassifierStage):
             self.engine.sync_shadow()
         self.val_acc = torch.zeros(6, dtype=torch.float32, device=self.device)
         self.val_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # what render() draws: the side of the square image and its background
+        # (a grey level or an (r, g, b) triple); evaluation.Tester sets both
+        self.renderings_size = 256
+        self.renderings_background = 0.0
 
     # ------------------------------------------------------------ properties
     @property
@@ -331,16 +336,19 @@ class ModelManager(ClassifierStage):
     def render(self, batched_verts, vertex_errors=None, error_max_scale=None):
         """``ModelManager.render`` (``model_manager.py:625-658``): the meshes
         ``batched_verts`` ``[B, V, 3]`` (un-normalised) seen from ``dist=2.5,
-        elev=0, azim=15`` at 256 x 256, ``[B, 3, 256, 256]`` on the device.
+        elev=0, azim=15`` at ``renderings_size`` (256) squared over
+        ``renderings_background`` (0.0), ``[B, 3, S, S]`` on the device.
         Without ``vertex_errors``: grey 0.5, Gouraud-shaded under a point
         light at (0, 0, 3).  With ``vertex_errors`` ``[B, V]``: their plasma
         colours over ``[0, error_max_scale]``, unshaded."""
         from . import rendering
         verts = batched_verts.detach().to(self.device, torch.float32).contiguous()
         if vertex_errors is None:
-            return rendering.render(verts, self.template_faces, shading="gouraud")
+            return rendering.render(verts, self.template_faces, shading="gouraud", image_size=self.renderings_size,
+                                    background=self.renderings_background)
         colors = rendering.errors_to_colors(vertex_errors.to(self.device), 0, error_max_scale)
-        return rendering.render(verts, self.template_faces, colors, shading="none")
+        return rendering.render(verts, self.template_faces, colors, shading="none", image_size=self.renderings_size,
+                                background=self.renderings_background)
 
     @torch.no_grad()
     def log_images(self, in_data, out_dir, epoch, normalization_dict=None, phase="train", error_max_scale=5):

@@ -875,6 +875,65 @@ def vertex_errors(out, gt, to_mm=89.11, mean=None, std=None, want_l1=False, want
     return (err,) + ((l1,) if want_l1 else ()) + ((mm,) if want_mesh_mean else ())
 
 
+RM_MAX_REGIONS = 64  # CFSD_RM_MAX_REGIONS
+RM_THREADS = 256     # CFSD_RM_THREADS
+
+
+def group_vertex_errors(frames, n, to_mm=89.11, mean=None, std=None):
+    """Distance of every frame of a traversal to its group's first frame
+    (``Tester.latent_traversals``, ``test.py:157-158``: ``compute_vertex_errors``
+    against ``gen_verts[0].expand(...)``) for ``G`` groups of ``n`` consecutive
+    frames at once: ``frames`` ``[G*n, V, 3]`` -> ``err`` ``[G*n, V]``, bit-equal
+    to :func:`vertex_errors` on the expanded first frames, which are read in
+    place.  ``mean``/``std`` ``[V, 3]`` un-normalise first."""
+    _need(frames, None, name="frames")
+    if frames.dim() != 3 or frames.shape[-1] != 3:
+        raise ValueError(f"frames: shape {tuple(frames.shape)}, expected [G*n, V, 3]")
+    total, nv = int(frames.shape[0]), int(frames.shape[1])
+    n = int(n)
+    if n < 1 or total < 1 or nv < 1 or total % n:
+        raise ValueError(f"{total} frames of {nv} vertices do not form groups of n={n}")
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std go together")
+    if mean is not None:
+        _need(mean, (nv, 3), name="mean")
+        _need(std, (nv, 3), name="std")
+    err = torch.empty((total, nv), dtype=torch.float32, device=frames.device)
+    call("cfsd_group_vertex_errors", ptr(frames), ptr(mean), ptr(std), ptr(err), total // n, n, nv, float(to_mm),
+         stream_ptr())
+    return err
+
+
+def region_means_depth(length):
+    """``CFSD_RM_DEPTH``: the longest chain of additions one term of a list of
+    ``length`` entries passes through in :func:`region_means`, plus one for
+    the division."""
+    return -(-int(length) // RM_THREADS) + 9
+
+
+def region_means(values, region_csr):
+    """Per-region mean of a per-vertex quantity (``test.py:208-215``):
+    ``values`` ``[rows, V]``, ``region_csr`` a :class:`topology.RegionCSR`
+    (``DeviceTopology.region_csr``) -> ``[rows, R]``, in a fixed summation
+    order per (row, region) (``include/cfsd.h``)."""
+    _need(values, None, name="values")
+    if values.dim() != 2 or values.shape[0] < 1:
+        raise ValueError(f"values: shape {tuple(values.shape)}, expected [rows >= 1, V]")
+    rows, nv = int(values.shape[0]), int(values.shape[1])
+    if nv != region_csr.nv:
+        raise ValueError(f"values: {nv} columns, the regions index {region_csr.nv} vertices")
+    n_regions = region_csr.n_regions
+    if not 1 <= n_regions <= RM_MAX_REGIONS:
+        raise ValueError(f"{n_regions} regions: 1..{RM_MAX_REGIONS} are supported")
+    _need(region_csr.idx, (region_csr.nnz,), torch.int32, "region_csr.idx")
+    if region_csr.idx.device != values.device:
+        raise ValueError(f"region_csr is on {region_csr.idx.device}, values on {values.device}")
+    out = torch.empty((rows, n_regions), dtype=torch.float32, device=values.device)
+    call("cfsd_region_means", ptr(values), region_csr.ptr_host.ctypes.data_as(ctypes.c_void_p), ptr(region_csr.idx),
+         ptr(out), rows, nv, n_regions, stream_ptr())
+    return out
+
+
 def reconstruction_error_stats(mesh_means):
     """The summary of ``Tester.reconstruction_errors`` (``test.py:298-301``)
     over the concatenated per-mesh means (device tensor, torch reductions)."""

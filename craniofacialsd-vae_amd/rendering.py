@@ -187,3 +187,41 @@ def save_png(path, image):
     with open(path, "wb") as f:
         f.write(data)
     return path
+
+
+def save_apng(path, frames, fps):
+    """Write ``frames`` ``[N, 3, H, W]`` (float in [0, 1], clamped; or uint8;
+    each quantised by :func:`to_uint8`) as an animated PNG that loops for ever
+    at ``fps`` frames per second (the reference writes mp4 files through
+    ``torchvision.io.write_video``): ``acTL``, then per frame an ``fcTL`` and
+    its image (``IDAT`` for the first frame, ``fdAT`` for the others), the
+    ``fcTL`` / ``fdAT`` sequence numbers running from 0.  A viewer without
+    APNG support shows the first frame."""
+    if frames.dim() != 4 or frames.shape[1] != 3 or frames.shape[0] < 1:
+        raise ValueError(f"frames: shape {tuple(frames.shape)}, expected [N >= 1, 3, H, W]")
+    if not fps > 0:
+        raise ValueError(f"fps {fps} must be positive")
+    from fractions import Fraction
+    delay = Fraction(1.0 / float(fps)).limit_denominator(65535)
+    if not 0 < delay.numerator <= 65535:
+        raise ValueError(f"fps {fps}: the frame delay does not fit the format's 16-bit fraction")
+    n, _, h, w = frames.shape
+    out = [b"\x89PNG\r\n\x1a\n", _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)),
+           _chunk(b"acTL", struct.pack(">II", n, 0))]
+    seq = 0
+    for k in range(n):
+        rgb = to_uint8(frames[k])
+        rows = np.concatenate([np.zeros((h, 1), np.uint8), rgb.reshape(h, w * 3)], axis=1)  # filter type 0 per row
+        data = zlib.compress(rows.tobytes(), 6)
+        out.append(_chunk(b"fcTL", struct.pack(">IIIIIHHBB", seq, w, h, 0, 0, delay.numerator, delay.denominator,
+                                               0, 0)))
+        seq += 1
+        if k == 0:
+            out.append(_chunk(b"IDAT", data))
+        else:
+            out.append(_chunk(b"fdAT", struct.pack(">I", seq) + data))
+            seq += 1
+    out.append(_chunk(b"IEND", b""))
+    with open(path, "wb") as f:
+        f.write(b"".join(out))
+    return path

@@ -17,7 +17,9 @@ tables the kernels read:
   the reference's sequential ``scatter_add`` order) and the transpose CSR
   for the backward;
 * the Laplacian -> CSR in coalesced (row, col) order + transpose CSR;
-* the feature-swap regions -> a ``[n_regions, V]`` uint8 membership mask.
+* the feature-swap regions -> a ``[n_regions, V]`` uint8 membership mask and,
+  on first use, a CSR of their vertex lists (``region_csr``: the per-region
+  means of the evaluation harness).
 """
 import numpy as np
 import torch
@@ -160,6 +162,31 @@ class Level:
     """Device tables of one resolution level."""
 
 
+class RegionCSR:
+    """The regions' vertex lists as a CSR, in ``region_keys`` order: ``ptr``
+    ``[R + 1]`` and ``idx`` ``[nnz]`` int32 on the device, ``ptr_host`` the
+    same row pointer as a NumPy array (``cfsd_region_means`` reads it on the
+    host), ``nv`` the vertex count the lists were checked against.  The lists
+    keep their stored order; they may overlap."""
+
+    def __init__(self, regions, nv, device="cuda"):
+        lists = [np.asarray(r, np.int64).reshape(-1) for r in regions]
+        if not lists:
+            raise ValueError("no regions")
+        for k, lst in enumerate(lists):
+            if lst.size == 0:
+                raise ValueError(f"region {k} is empty")
+            if lst.min() < 0 or lst.max() >= nv:
+                raise ValueError(f"region {k}: vertex index outside [0, {nv})")
+        self.nv = int(nv)
+        self.n_regions = len(lists)
+        self.lengths = [int(lst.size) for lst in lists]
+        self.ptr_host = _i32(np.concatenate([[0], np.cumsum(self.lengths)]))
+        self.nnz = int(self.ptr_host[-1])
+        self.ptr = _dev(self.ptr_host, device)
+        self.idx = _dev(_i32(np.concatenate(lists)), device)
+
+
 def _dev(a, device):
     return torch.from_numpy(np.ascontiguousarray(a)).to(device)
 
@@ -257,12 +284,25 @@ class DeviceTopology:
             self.lapT_csr = self._csr(csr_transpose_from_coo(r, c, v, lshape[1]))
         self.region_mask = None
         self.n_regions = 0
+        self._regions = None if regions is None else [np.asarray(f, np.int64) for f in regions]
+        self._region_csr = None
         if regions is not None:
             mask = np.zeros((len(regions), self.n_verts[0]), np.uint8)
             for k, feat in enumerate(regions):
                 mask[k, np.asarray(feat, np.int64)] = 1
             self.region_mask = _dev(mask, self.device)
             self.n_regions = len(regions)
+
+    @property
+    def region_csr(self):
+        """:class:`RegionCSR` of the ``regions`` lists (the ones behind
+        ``region_mask``), built on first use.  ``ValueError`` for a topology
+        without regions, an empty region or an index out of range."""
+        if self._region_csr is None:
+            if self._regions is None:
+                raise ValueError("the topology has no regions")
+            self._region_csr = RegionCSR(self._regions, self.n_verts[0], self.device)
+        return self._region_csr
 
     def _csr(self, t):
         ptr, col, val = t

@@ -20,8 +20,9 @@ With a ``classifier:`` section in the configuration the lead rank then runs
 the classifier stage (train.py:76-77, model_manager.py:448-504): the MLP
 classifier, LDA, QDA and the region LDAs / QDAs on the eval-mode latents, their
 files written next to the checkpoints and the validation accuracies to
-``<output>/classifiers.json``.  Latent traversal videos and the ``LinearSVC``
-are out of scope.
+``<output>/classifiers.json``.  The ``LinearSVC`` is out of scope; latent
+traversals and the rest of the reference's ``test.py`` run are ``evaluate.py``
+(``evaluation.Tester``).
 """
 import argparse
 import json

@@ -1,0 +1,21 @@
+"""``python evaluate.py --id ID [--output_path P] [--precision fp32|bf16] [--seed S]
+[--no-animations] [--diversity-samples N] [--only NAME[,NAME]]``: evaluate the
+model trained as ``ID`` (the reference's ``python test.py --id ID``,
+test.py:57-79, 1443-1480) on the MI355X path
+(craniofacialsd-vae_amd/evaluation.py): latent traversals with their
+per-region table, random generation, reconstruction errors and the two
+diversity figures (``eval_metrics.json``) and, when the run trained
+classifiers, their test reports.  Everything is written into
+``<output_path>/outputs/<ID>``.  ``--only`` runs single steps: traversals,
+embeddings, classifiers, generation, metrics, interpolate."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cfsd_loader  # noqa: E402
+
+cfsd_loader.load()
+from craniofacialsd_vae_amd.evaluation import evaluate_main  # noqa: E402
+
+if __name__ == "__main__":
+    evaluate_main()

@@ -607,6 +607,45 @@ int cfsd_vertex_errors(const float* out, const float* gt, const float* mean, con
                        float* err, float* l1, float* mesh_mean, int batch, int nv, float to_mm,
                        void* stream);
 
+/* The two device reductions of a latent traversal (Tester.latent_traversals,
+ * test.py:128-229), ABI 4.17.  Plain fp32, no atomics; neither result depends
+ * on the launch geometry or on the other rows of the call.
+ *
+ * cfsd_group_vertex_errors replaces compute_vertex_errors on (frames, frame 0
+ * of each traversal expanded to its length) (test.py:157-158):
+ * frames [groups * n, nv, 3] = `groups` groups of n consecutive frames;
+ * mean/std [nv, 3] (both NULL = no un-normalisation, else u = x*std + mean);
+ *   err[g*n + k, v] = sqrt(sum_c (u(frames[g*n + k, v, c]) - u(frames[g*n, v, c]))^2) * to_mm
+ * with the operations of cfsd_vertex_errors in its order (contraction off):
+ * err is bit-equal to cfsd_vertex_errors(out = frames, gt = frame 0 of every
+ * group repeated n times), and err[g*n, :] is exactly 0.  Frame 0 is read in
+ * place; no expanded copy exists.  groups, n, nv >= 1; groups*n*nv*3 < 2^31.
+ *
+ * cfsd_region_means replaces the per-region mean of a per-vertex quantity
+ * (test.py:208-215: fancy indexing + torch.mean per region and row, collected
+ * through pandas): values [rows, nv]; region_ptr a HOST array of
+ * n_regions + 1 int32 and region_idx [region_ptr[n_regions]] int32 on the
+ * device form a CSR of vertex lists (lists may overlap, need not be sorted);
+ *   out[b, r] = (sum_j values[b, region_idx[j]]) / len_r,  j over list r.
+ * Summation scheme: one CFSD_RM_THREADS-thread workgroup per (b, r); thread t
+ * adds entries t, t + 256, t + 512, ... of the list in ascending order onto 0,
+ * the 256 partials are added in a halving tree (part[t] += part[t + w], w =
+ * 128, 64, ..., 1), the total is divided by len_r.  Depth (the longest chain of
+ * additions one term passes through, plus one for the division):
+ *   CFSD_RM_DEPTH(len) = ceil(len / 256) + 8 + 1,
+ * 25 for a list of 4096 entries, 21 for the template's longest (3017).
+ * CFSD_EINVAL without a launch: a null pointer, sizes < 1, n_regions >
+ * CFSD_RM_MAX_REGIONS, region_ptr[0] != 0, a decreasing region_ptr, an empty
+ * list.  The entries of region_idx must lie in [0, nv): they are not read on
+ * the host here; the caller checks them once when it builds the CSR. */
+#define CFSD_RM_MAX_REGIONS 64
+#define CFSD_RM_THREADS 256
+#define CFSD_RM_DEPTH(len) (((len) + CFSD_RM_THREADS - 1) / CFSD_RM_THREADS + 9)
+int cfsd_group_vertex_errors(const float* frames, const float* mean, const float* std, float* err, int groups,
+                             int n, int nv, float to_mm, void* stream);
+int cfsd_region_means(const float* values, const int32_t* region_ptr, const int32_t* region_idx, float* out,
+                      int rows, int nv, int n_regions, void* stream);
+
 /* ---------------------------------------------------------------- latent fitting
  * The Chamfer term of Tester.fit_mesh (test.py:404-405, 427-429:
  * pytorch3d.loss.chamfer_distance between the decoded heads and an
