@@ -127,6 +127,8 @@ SIGNATURES = {
     "cfsd_mlp_workspace": (_Z, [_P, _I, _I]),
     "cfsd_mlp_train_steps": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F,
                                   _F, _F, _P]),
+    "cfsd_mlp_head_step": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _I, _F, _P, _I, _I, _I,
+                                _F, _F, _F, _F, _F, _P]),
 }
 
 

@@ -33,12 +33,14 @@ MAIN_MODEL_TYPES = ("mlp", "lda", "qda", "none")
 
 
 # ---------------------------------------------------------------- configuration
-def classifier_params(config):
+def classifier_params(config, *, end2end=False):
     """The validated ``classifier:`` section of a configuration, or None when
     there is none (then nothing of this module is constructed).  ``svm``
-    (liblinear's coordinate descent has no place on this path) and
-    ``mlp_training_type: end2end`` (a classifier loss inside the fused VAE
-    step) are refused."""
+    (liblinear's coordinate descent has no place on this path) is refused.
+    ``mlp_training_type: end2end`` (the classifier's loss inside the VAE step)
+    is accepted only from a caller that trains it there (``end2end=True``:
+    ``manager.ModelManager``); it then needs a finite ``mlp_loss_weight`` and
+    an ``optimization.batch_size`` the head kernel takes (<= 16)."""
     p = config.get("classifier")
     if p is None:
         return None
@@ -48,9 +50,23 @@ def classifier_params(config):
                          "package); use mlp, lda or qda")
     if main not in MAIN_MODEL_TYPES:
         raise ValueError(f"classifier.main_model_type: {main!r}, expected one of {MAIN_MODEL_TYPES}")
+    if str(p.get("mlp_training_type", "after")) == "end2end" and end2end:
+        w = p.get("mlp_loss_weight")
+        try:  # (PyYAML reads 1e-3 as a string: numbers are taken as the other weights are, through float())
+            ok = not isinstance(w, bool) and math.isfinite(float(w))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"classifier.mlp_loss_weight: {w!r}, a finite number is required with "
+                             "mlp_training_type: end2end")
+        bs = int(config.get("optimization", {}).get("batch_size", 1))
+        if bs > ops.MLP_MAX_BS:
+            raise ValueError(f"optimization.batch_size {bs}: mlp_training_type: end2end takes at most "
+                             f"{ops.MLP_MAX_BS}")
+        return dict(p)
     if str(p.get("mlp_training_type", "after")) == "end2end":
         raise NotImplementedError("classifier.mlp_training_type: end2end (the classifier loss inside the VAE "
-                                  "step) is not implemented; use 'after'")
+                                  "step) is not implemented by this caller; use 'after'")
     if str(p.get("mlp_training_type", "after")) != "after":
         raise ValueError(f"classifier.mlp_training_type: {p.get('mlp_training_type')!r}, expected 'after'")
     return dict(p)
@@ -368,11 +384,14 @@ class ClassifierStage:
     ``manager.ModelManager``; without the section ``_init_classifiers`` leaves
     ``_classifier_params = None`` and constructs nothing."""
 
-    def _init_classifiers(self, configurations, seed=0):
-        self._classifier_params = classifier_params(configurations)
+    def _init_classifiers(self, configurations, seed=0, end2end=False):
+        """``end2end``: the caller can train the MLP inside the VAE step."""
+        self._classifier_params = classifier_params(configurations, end2end=end2end)
         self._class2idx_dict, self._class_weights = None, None
+        self._mlp_end2end = False
         if self._classifier_params is None:
             return
+        self._mlp_end2end = str(self._classifier_params.get("mlp_training_type", "after")) == "end2end"
         from .data import labels_of
         cp = self._classifier_params
         names = [n for n in os.listdir(configurations["data"]["dataset_path"]) if n.endswith(".obj")]
@@ -437,7 +456,9 @@ class ClassifierStage:
     def train_and_validate_classifiers(self, train_set, val_set, writer, checkpoint_dir):
         """``model_manager.py:448-504`` without the SVM: ``mlp_epochs`` epochs
         of the MLP in batches of ``batch_size`` consecutive latents (scalars
-        ``{train,validation}/class_{loss,acc}`` per epoch), LDA and QDA on the
+        ``{train,validation}/class_{loss,acc}`` per epoch; none with
+        ``mlp_training_type: end2end``, whose MLP was trained inside the VAE
+        step and is only validated here, ``:457``), LDA and QDA on the
         full latent, one LDA / QDA per latent region when the latent
         consistency weight is above 0; the five files are written into
         ``checkpoint_dir``.  Returns the validation accuracies in percent
@@ -449,7 +470,7 @@ class ClassifierStage:
         z, y = self._classifier_rows(train_set)
         zv, yv = self._classifier_rows(val_set) if val_set is not None else (None, None)
         mlp, w = self.classifier_mlp, self._class_weights
-        for epoch in range(int(cp["mlp_epochs"])):
+        for epoch in range(0 if self._mlp_end2end else int(cp["mlp_epochs"])):
             tr_loss, tr_acc = mlp.run_epoch(z, y, w, self.bs, train=True)
             if writer is not None:
                 writer.add_scalar("train/class_loss", tr_loss, epoch + 1)

@@ -31,7 +31,11 @@
 // (forward, weighted cross-entropy, activation gradients; layer inputs x_l
 // and output gradients dy_l left in the workspace), the second covers the
 // parameters: each thread forms its element's gradient (<= 16 terms,
-// ascending row) and applies Adam in place.
+// ascending row) and applies Adam in place.  The same two launches serve as a
+// head of the VAE step (cfsd_mlp_head_step, mlp_training_type: end2end,
+// model_manager.py:295-318): rows strided through the step's latent codes,
+// labels gathered through its batch indices, the backward continued one layer
+// into the latent gradient, the parameters' gradient scaled by the loss weight.
 #include <math.h>
 
 #include "cfsd_common.h"
@@ -376,15 +380,30 @@ __global__ __launch_bounds__(kMlpFwdThreads) void mlp_fwd_k(MlpDesc D, const flo
   }
 }
 
-// First launch of a step, ONE workgroup: forward of rows [row_base, +bs),
-// loss / accuracy into acc[3], and (train) the activation gradients.
-template <int RB>
-__global__ __launch_bounds__(kMlpStepThreads) void mlp_step_k(MlpDesc D, const float* __restrict__ z,
-                                                              const int* __restrict__ label,
-                                                              const float* __restrict__ cw,
-                                                              const float* __restrict__ params, float* __restrict__ ws,
-                                                              float* __restrict__ acc, int* __restrict__ step,
-                                                              long row_base, int bs, int train) {
+// What the head step (cfsd_mlp_head_step) adds to a step's first launch: rows
+// strided through z, labels looked up through the step's batch indices, and
+// (train) the gradient w.r.t. the input rows added to dlat.
+struct MlpHead {
+  const int* batch_idx;    // [bs] rows of label_table
+  const int* label_table;  // [n_labels] class indices
+  float* dlat;             // row i at dlat + i * dlat_stride; the first dims[0] columns gain w_cls * dz_i
+  long z_stride, dlat_stride;
+  int n_labels;
+  float w_cls;
+};
+
+// First launch of a step, ONE workgroup: forward of bs rows, loss / accuracy
+// into acc[3], and (train) the activation gradients.  HEAD = false
+// (cfsd_mlp_train_steps): rows [row_base, +bs) of z [*, dims[0]], labelled by
+// row number.  HEAD = true (cfsd_mlp_head_step): row i at z + i * H.z_stride,
+// labelled label_table[batch_idx[i]], and the backward continues through
+// layer 0 into H.dlat.
+template <int RB, bool HEAD>
+__device__ __forceinline__ void mlp_step_body(const MlpDesc& D, const float* __restrict__ z,
+                                              const int* __restrict__ label, const float* __restrict__ cw,
+                                              const float* __restrict__ params, float* __restrict__ ws,
+                                              float* __restrict__ acc, int* __restrict__ step, long row_base, int bs,
+                                              int train, const MlpHead& H) {
   extern __shared__ float mlp_lds[];
   __shared__ float s_li[kMlpMaxBs], s_wi[kMlpMaxBs], s_lse[kMlpMaxBs];
   __shared__ int s_y[kMlpMaxBs], s_ok[kMlpMaxBs];
@@ -395,7 +414,15 @@ __global__ __launch_bounds__(kMlpStepThreads) void mlp_step_k(MlpDesc D, const f
   float* A = mlp_lds;
   float* B = mlp_lds + RB * (train ? kMlpMaxWidth : ldx);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  mlp_load_rows<RB>(z, row_base, bs, D.dims[0], A, ldx);
+  if constexpr (HEAD) {
+    const int n0 = D.dims[0];
+    for (int e = threadIdx.x; e < RB * n0; e += blockDim.x) {
+      const int i = e / n0, k = e - i * n0;
+      A[i * ldx + k] = i < bs ? z[i * H.z_stride + k] : 0.f;
+    }
+  } else {
+    mlp_load_rows<RB>(z, row_base, bs, D.dims[0], A, ldx);
+  }
   __syncthreads();
   for (int l = 0; l < L; ++l) {
     const int n_in = D.dims[l], n_out = D.dims[l + 1];
@@ -438,7 +465,12 @@ __global__ __launch_bounds__(kMlpStepThreads) void mlp_step_k(MlpDesc D, const f
 #pragma unroll
     for (int off = 32; off; off >>= 1) se += __shfl_xor(se, off);
     if (lane == 0) {
-      const int y = min(max(label[row_base + wave], 0), C - 1);
+      int y;
+      if constexpr (HEAD)
+        y = H.label_table[min(max(H.batch_idx[wave], 0), H.n_labels - 1)];
+      else
+        y = label[row_base + wave];
+      y = min(max(y, 0), C - 1);
       const float lse = m + logf(se);
       s_y[wave] = y;
       s_lse[wave] = lse;
@@ -479,8 +511,9 @@ __global__ __launch_bounds__(kMlpStepThreads) void mlp_step_k(MlpDesc D, const f
   __syncthreads();
   // dy_{l-1} = (dy_l W_l) * [x_l > 0].  Wave (tile, g): input columns
   // [64 tile, +64), output neurons g, g + G, ...; the G partials of a column
-  // are added in ascending g.
-  for (int l = L - 1; l >= 1; --l) {
+  // are added in ascending g.  HEAD: one layer further, dz = dy_0 W_0 (no
+  // mask: the input is z), added to dlat by the thread that owns the element.
+  for (int l = L - 1; l >= (HEAD ? 0 : 1); --l) {
     const int n_in = D.dims[l], n_out = D.dims[l + 1];
     const int tiles = (n_in + 63) / 64, G = nw / tiles, pld = tiles * 64;
     const int tile = wave % tiles, g = wave / tiles, k = tile * 64 + lane;
@@ -514,6 +547,16 @@ __global__ __launch_bounds__(kMlpStepThreads) void mlp_step_k(MlpDesc D, const f
       for (int i = 0; i < RB; ++i) B[(g * RB + i) * pld + k] = a[i];
     }
     __syncthreads();
+    if (HEAD && l == 0) {
+      for (int e = threadIdx.x; e < bs * n_in; e += blockDim.x) {
+        const int i = e / n_in, kk = e - i * n_in;
+        float s = B[i * pld + kk];
+        for (int gg = 1; gg < G; ++gg) s += B[(gg * RB + i) * pld + kk];
+        float* d = H.dlat + i * H.dlat_stride + kk;
+        *d = fmaf(H.w_cls, s, *d);
+      }
+      return;
+    }
     const float* xl = ws + (long)bs * mlp_x_off(D, l);
     float* dy = ws + (long)bs * mlp_dy_off(D, l - 1);
     for (int e = threadIdx.x; e < bs * n_in; e += blockDim.x) {
@@ -528,11 +571,33 @@ __global__ __launch_bounds__(kMlpStepThreads) void mlp_step_k(MlpDesc D, const f
   }
 }
 
-// Second launch of a step: one thread per parameter.
+template <int RB>
+__global__ __launch_bounds__(kMlpStepThreads) void mlp_step_k(MlpDesc D, const float* __restrict__ z,
+                                                              const int* __restrict__ label,
+                                                              const float* __restrict__ cw,
+                                                              const float* __restrict__ params, float* __restrict__ ws,
+                                                              float* __restrict__ acc, int* __restrict__ step,
+                                                              long row_base, int bs, int train) {
+  mlp_step_body<RB, false>(D, z, label, cw, params, ws, acc, step, row_base, bs, train, MlpHead{});
+}
+
+template <int RB>
+__global__ __launch_bounds__(kMlpStepThreads) void mlp_head_k(MlpDesc D, const float* __restrict__ z,
+                                                              const float* __restrict__ cw,
+                                                              const float* __restrict__ params, float* __restrict__ ws,
+                                                              float* __restrict__ acc, int* __restrict__ step, int bs,
+                                                              int train, MlpHead H) {
+  mlp_step_body<RB, true>(D, z, nullptr, cw, params, ws, acc, step, 0, bs, train, H);
+}
+
+// Second launch of a step: one thread per parameter.  HEAD: the gradient is
+// that of w_cls * loss (gscale = w_cls), and without moments (m == NULL) it is
+// only written out (the data-parallel step: Adam follows the all-reduce).
+template <bool HEAD>
 __global__ __launch_bounds__(256) void mlp_adam_k(MlpDesc D, float* __restrict__ params, float* __restrict__ m,
                                                   float* __restrict__ v, const float* __restrict__ ws,
                                                   const int* __restrict__ step, float* __restrict__ dw_out, int bs,
-                                                  float lr, float b1, float b2, float eps, float wd) {
+                                                  float lr, float b1, float b2, float eps, float wd, float gscale) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= D.total) return;
   int l = 0;
@@ -548,7 +613,9 @@ __global__ __launch_bounds__(256) void mlp_adam_k(MlpDesc D, float* __restrict__
     const int o = local - n_out * n_in;
     for (int i = 0; i < bs; ++i) g += dy[i * n_out + o];
   }
+  if constexpr (HEAD) g *= gscale;
   if (dw_out) dw_out[e] = g;
+  if (HEAD && !m) return;
   const int t = *step;
   const float bc1 = 1.f - powf(b1, (float)t);
   const float sqrt_bc2 = sqrtf(1.f - powf(b2, (float)t));
@@ -665,8 +732,8 @@ static int mlp_steps_launch(const MlpDesc& D, const float* z, const int32_t* lab
     hipLaunchKernelGGL(mlp_step_k<RB>, dim3(1), dim3(kMlpStepThreads), lds, st, D, z, label, cw, params, ws, acc,
                        step, row0 + (long)t * bs, bs, train);
     if (train)
-      hipLaunchKernelGGL(mlp_adam_k, dim3((D.total + 255) / 256), dim3(256), 0, st, D, params, m, v, ws, step, dw_out,
-                         bs, lr, b1, b2, eps, wd);
+      hipLaunchKernelGGL(mlp_adam_k<false>, dim3((D.total + 255) / 256), dim3(256), 0, st, D, params, m, v, ws, step,
+                         dw_out, bs, lr, b1, b2, eps, wd, 1.f);
   }
   return launch_status("mlp_train_steps");
 }
@@ -696,4 +763,72 @@ extern "C" int cfsd_mlp_train_steps(const float* z, const int32_t* label, const 
     default: CFSD_MLP_STEPS(16);
   }
 #undef CFSD_MLP_STEPS
+}
+
+template <int RB>
+static int mlp_head_launch(const MlpDesc& D, const float* z, const float* cw, float* params, float* m, float* v,
+                           int32_t* step, float* acc, float* ws, float* dw_out, const MlpHead& H, int bs, int train,
+                           float lr, float b1, float b2, float eps, float wd, hipStream_t st) {
+  const size_t lds = (size_t)2 * RB * (train ? kMlpMaxWidth : D.maxw) * 4;
+  // the limit is raised once per instantiation and device (to the train
+  // step's size, the larger one: the attribute belongs to the current device's
+  // function), so nothing but launches is issued when a step is recorded
+  constexpr int kMaxDevices = 64;
+  static bool raised[kMaxDevices] = {};
+  int device = 0;
+  if (hipGetDevice(&device) != hipSuccess) return set_error(CFSD_EINVAL, "mlp_head_step: no current device");
+  const bool known = device >= 0 && device < kMaxDevices;
+  if (!known || !raised[device]) {
+    if (int rc = mlp_raise_lds("mlp_head_step", (const void*)mlp_head_k<RB>, (size_t)2 * RB * kMlpMaxWidth * 4))
+      return rc;
+    if (known) raised[device] = true;
+  }
+  hipLaunchKernelGGL(mlp_head_k<RB>, dim3(1), dim3(kMlpStepThreads), lds, st, D, z, cw, params, ws, acc, step, bs,
+                     train, H);
+  if (train)
+    hipLaunchKernelGGL(mlp_adam_k<true>, dim3((D.total + 255) / 256), dim3(256), 0, st, D, params, m, v, ws, step,
+                       dw_out, bs, lr, b1, b2, eps, wd, H.w_cls);
+  return launch_status("mlp_head_step");
+}
+
+extern "C" int cfsd_mlp_head_step(const float* z, int ld_z, int row_stride, const int32_t* batch_idx,
+                                  const int32_t* label_table, int n_labels, const float* class_weight,
+                                  float* params, float* m, float* v, int32_t* step, float* acc, void* workspace,
+                                  size_t workspace_bytes, float* dw_out, float* dlat, int ld_dlat, float w_cls,
+                                  const int* dims, int n_layers, int bs, int train, float lr, float beta1,
+                                  float beta2, float eps, float weight_decay, void* stream) {
+  MlpDesc D;
+  if (int rc = mlp_describe("mlp_head_step", dims, n_layers, D)) return rc;
+  if (bs < 1 || bs > kMlpMaxBs) return set_error(CFSD_EINVAL, "mlp_head_step: batch %d (1..%d)", bs, kMlpMaxBs);
+  if (row_stride < 1 || ld_z < D.dims[0] || n_labels < 1)
+    return set_error(CFSD_EINVAL, "mlp_head_step: bad sizes row_stride=%d ld_z=%d (width %d) n_labels=%d",
+                     row_stride, ld_z, D.dims[0], n_labels);
+  if (!z || !batch_idx || !label_table || !class_weight || !params || !acc)
+    return set_error(CFSD_EINVAL, "mlp_head_step: null pointer");
+  if (train) {
+    if (!step || !dlat || (!m != !v) || (!m && !dw_out))
+      return set_error(CFSD_EINVAL, "mlp_head_step: a train step needs step, dlat and either m and v or dw_out");
+    if (ld_dlat < D.dims[0]) return set_error(CFSD_EINVAL, "mlp_head_step: ld_dlat %d < width %d", ld_dlat, D.dims[0]);
+    const size_t need = (size_t)bs * mlp_dy_off(D, n_layers) * 4;
+    if (!workspace || workspace_bytes < need)
+      return set_error(CFSD_EINVAL, "mlp_head_step: workspace %zu < %zu bytes", workspace_bytes, need);
+  }
+  MlpHead H;
+  H.batch_idx = batch_idx;
+  H.label_table = label_table;
+  H.dlat = dlat;
+  H.z_stride = (long)row_stride * ld_z;
+  H.dlat_stride = (long)row_stride * ld_dlat;
+  H.n_labels = n_labels;
+  H.w_cls = w_cls;
+  const hipStream_t st = (hipStream_t)stream;
+#define CFSD_MLP_HEAD(RB)                                                                                       \
+  return mlp_head_launch<RB>(D, z, class_weight, params, m, v, step, acc, (float*)workspace, dw_out, H, bs,     \
+                             train ? 1 : 0, lr, beta1, beta2, eps, weight_decay, st)
+  switch (mlp_rows_tile(bs)) {
+    case 4: CFSD_MLP_HEAD(4);
+    case 8: CFSD_MLP_HEAD(8);
+    default: CFSD_MLP_HEAD(16);
+  }
+#undef CFSD_MLP_HEAD
 }

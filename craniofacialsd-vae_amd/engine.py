@@ -129,6 +129,20 @@ class _Buffers:
     pass
 
 
+class ClassifierHead:
+    """The MLP classifier trained inside the VAE step (``mlp_training_type:
+    end2end``): what :meth:`SDVAEEngine.attach_classifier_head` keeps."""
+
+    def __init__(self, mlp, class_weights, w_cls, keep_grad=False):
+        self.mlp, self.cw, self.w_cls = mlp, class_weights, float(w_cls)
+        # one GPU: also store the parameters' gradient in ``grad`` (the Adam launch needs no gradient
+        # buffer; tests and diagnostics ask for it).  Data-parallel steps always fill ``grad``.
+        self.keep_grad = bool(keep_grad)
+        dev = mlp.flat.device
+        self.grad = torch.zeros_like(mlp.flat)  # the data-parallel step's third gradient bucket
+        self.ws = torch.empty(ops.mlp_workspace(mlp.dims, ops.MLP_MAX_BS) // 4 + 1, dtype=torch.float32, device=dev)
+
+
 class SDVAEEngine:
     """Forward/backward/Adam of the SD-VAE on one device, for a fixed
     topology and any number of batch sizes (buffers cached per batch)."""
@@ -212,6 +226,9 @@ class SDVAEEngine:
         self.reset_parameters()
         self._bufs = {}
         self.loss_acc = torch.zeros(6, dtype=torch.float32, device=self.device)
+        # end2end classifier head (attach_classifier_head): None = the step as it always was
+        self.head = None
+        self.cls_acc = torch.zeros(3, dtype=torch.float32, device=self.device)  # {loss, accuracy, steps} sums
         self.betas, self.adam_eps = (0.9, 0.999), 1e-8
         # device step counter: drives the VAE noise, swap key and batch order
         # of cfsd_step_begin (one per engine, re-seeded by resume())
@@ -565,6 +582,64 @@ class SDVAEEngine:
         else:
             ops.latent_fwd(*args)
 
+    # ----------------------------------------------------------- classifier head
+    def attach_classifier_head(self, mlp, class_weights, w_cls, keep_grad=False):
+        """Train ``mlp`` (:class:`classify.MLPClassifier`, ``latent`` inputs)
+        inside the step (``model_manager.py:295-318``): ``w_cls`` times its
+        ``CrossEntropyLoss(class_weights)`` on the step's base latents (the
+        diagonal of a swapped group) joins the loss, the gradient w.r.t. ``z``
+        reaches the encoder through ``dlat``, and the classifier takes its own
+        Adam step (``mlp.lr``, ``mlp.weight_decay``, ``mlp.step``).  Labels
+        come from the step's data set (``ResidentData.class_idx``).  Sums of
+        loss and accuracy go to ``cls_acc``.  ``keep_grad``: a single-GPU step
+        also leaves the classifier's gradient in ``head.grad``.  ``mlp = None``
+        detaches."""
+        if mlp is None:
+            self.head = None
+            return
+        if mlp.dims[0] != self.spec.latent:
+            raise ValueError(f"the classifier takes {mlp.dims[0]} inputs, the latent has {self.spec.latent}")
+        if self.swap_bs > ops.MLP_MAX_BS:
+            raise ValueError(f"batch size {self.swap_bs}: the classifier head takes 1..{ops.MLP_MAX_BS}")
+        if not math.isfinite(float(w_cls)):
+            raise ValueError(f"classifier loss weight {w_cls!r} is not finite")
+        cw = class_weights.to(self.device, torch.float32).contiguous()
+        if tuple(cw.shape) != (mlp.dims[-1],):
+            raise ValueError(f"class weights {tuple(cw.shape)}, the classifier has {mlp.dims[-1]} outputs")
+        self.head = ClassifierHead(mlp, cw, w_cls, keep_grad)
+
+    def _head_step(self, b, train, cls_acc=None, grad_only=False):
+        """The head's two launches, right after the latent head wrote z and
+        dlat.  Batches that are not a step's (``b.bsz != step_rows``) have no
+        base meshes to label and are left alone."""
+        H = self.head
+        if H is None or b.bsz != self.step_rows:
+            return
+        table = getattr(b, "class_idx", None)
+        if table is None:
+            if not train:  # an evaluation forward of unlabelled meshes: no classification term
+                return
+            raise ValueError("the classifier head needs the class indices of the step's data set "
+                             "(ResidentData.class_idx)")
+        mlp = H.mlp
+        kw = {}
+        if train:
+            kw = dict(step=mlp.step, dlat=b.dlat, w_cls=H.w_cls, workspace=H.ws, lr=mlp.lr,
+                      weight_decay=mlp.weight_decay, beta1=self.betas[0], beta2=self.betas[1], eps=self.adam_eps)
+            if grad_only:  # data-parallel: the gradient only, for the all-reduce
+                kw["dw_out"] = H.grad
+            else:  # Adam in place; the gradient is stored only on request
+                kw.update(m=mlp.exp_avg, v=mlp.exp_avg_sq, dw_out=H.grad if H.keep_grad else None)
+        ops.mlp_head_step(b.z, b.batch_idx, table, H.cw, mlp.flat, self.cls_acc if cls_acc is None else cls_acc,
+                          mlp.dims, self.swap_bs, row_stride=self.swap_bs + 1 if self.swap else 1, train=train, **kw)
+
+    def head_adam_step(self, grad_scale):
+        """Data-parallel: the classifier's Adam after its gradient's all-reduce."""
+        H = self.head
+        ops.adam_scaled(H.mlp.flat, H.grad, H.mlp.exp_avg, H.mlp.exp_avg_sq, H.mlp.step, grad_scale, H.mlp.lr,
+                        beta1=self.betas[0], beta2=self.betas[1], eps=self.adam_eps,
+                        weight_decay=H.mlp.weight_decay)
+
     def _fused_latent(self, b):
         return self.fuse_latent and ops.latent_linear_fwd_supported(
             b.bsz, self.spec.latent, self.params.view("de_layers.0.weight").shape[0])
@@ -608,12 +683,17 @@ class SDVAEEngine:
             ops.loss_finalize(b.partials, b.terms, b.losses, acc, b.bsz, T.n_verts[0], self.spec.in_ch,
                               self.w_kl, self.w_lc if self._lc_on(b) else 0.0, self.w_lap)
 
-    def forward(self, b, train=True, acc=None, finalize=True):
+    def forward(self, b, train=True, acc=None, finalize=True, cls_acc=None, head_grad_only=False):
         """``finalize=False``: the loss reduction is left to backward(), whose
-        first launch finalises it (one launch less per train step)."""
+        first launch finalises it (one launch less per train step).  With a
+        classifier head attached its step follows the latent head (``cls_acc``:
+        where its loss / accuracy sums go, default ``self.cls_acc``;
+        ``head_grad_only``: leave its Adam to :meth:`head_adam_step`)."""
         self.encode(b)
         fused = self._fused_latent(b)
         self.latent(b, train, dec_linear=fused)
+        if self.head is not None:
+            self._head_step(b, train, cls_acc, head_grad_only)
         self.decode(b, linear=not fused)
         if self.topo.lap_csr is not None:
             self.losses_fwd(b, acc, finalize)
@@ -825,17 +905,26 @@ class SDVAEEngine:
         drew the noise).  With ``advance`` the noise is drawn first."""
         if advance:
             self.advance_step(b)
-        self.forward(b, train=True, acc=acc, finalize=False)
+        head = self.head is not None and b.bsz == self.step_rows
+        self.forward(b, train=True, acc=acc, finalize=False, head_grad_only=grad_hook is not None)
         if hasattr(grad_hook, "bucket_ready"):  # dist.GradientAverager: overlapped buckets
+            if head:
+                grad_hook.bucket_ready(self.head.grad)
             self.backward(b, bucket_hook=grad_hook.bucket_ready)
             grad_hook.finish(self.params.grad)
+            if head and grad_hook.active and grad_hook.world > 1:
+                grad_hook.scale(self.head.grad, 1.0 / grad_hook.world)
         elif grad_hook is not None:
             self.backward(b)
             grad_hook(self.params.grad)
+            if head:
+                grad_hook(self.head.grad)
         else:  # nothing between the gradient and the update: Adam fused into the reduce
             self.backward(b, fuse_adam=True)
             return
         self.adam_step()
+        if head:
+            self.head_adam_step(1.0)
 
     def resident_step(self, b, data, acc=None, grad_hook=None):
         """Full reference step from a resident dataset (:class:`ResidentData`):
@@ -858,6 +947,7 @@ class SDVAEEngine:
         swapped batch only after :meth:`encode` / :meth:`forward` ran (that
         launch writes it); ``b.swap_from`` marks the pending swap."""
         b.swap_from = None
+        b.class_idx = getattr(data, "class_idx", None)  # the classifier head's label table (no launch)
         if self.swap and self._swap_in_conv_ok(b, data):
             b.swap_from = data.meshes  # the swap rides in the first Enblock's conv launch (encode)
         elif self.swap:
@@ -886,9 +976,13 @@ class ResidentData:
     every epoch) and ``drop_last`` semantics (data_loading.py:40-48).
     ``n_batches`` caps the steps per epoch (data-parallel shards whose sizes
     differ by one must all run the same number of steps, each step issuing
-    the same gradient all-reduces: :func:`dist.steps_per_epoch`)."""
+    the same gradient all-reduces: :func:`dist.steps_per_epoch`).
+    ``class_idx`` (optional; may be assigned later): the class index of every
+    mesh, int32 ``[N]`` on the device -- the labels of a step with a
+    classifier head (``SDVAEEngine.attach_classifier_head``)."""
 
-    def __init__(self, meshes, bs, rows=None, shuffle=True, norm=None, n_batches=None, inplace=False):
+    def __init__(self, meshes, bs, rows=None, shuffle=True, norm=None, n_batches=None, inplace=False,
+                 class_idx=None):
         if not meshes.is_cuda or meshes.dim() != 3:
             raise ValueError("meshes must be a [N, V, C] device tensor")
         if norm is not None:
@@ -922,3 +1016,16 @@ class ResidentData:
         if self.n_batches < 1:
             raise ValueError(f"{self.n_items} meshes < one batch of {self.bs}")
         self.shuffle = bool(shuffle)
+        self.class_idx = None
+        if class_idx is not None:
+            self.set_class_idx(class_idx)
+
+    def set_class_idx(self, class_idx):
+        """Class index of every mesh (any integer sequence of length N)."""
+        y = torch.as_tensor(class_idx).to(torch.int32).reshape(-1)
+        if y.numel() != self.meshes.shape[0]:
+            raise ValueError(f"{y.numel()} class indices for {self.meshes.shape[0]} meshes")
+        if self.class_idx is not None:  # in place: recorded steps hold this tensor's address
+            self.class_idx.copy_(y)
+        else:
+            self.class_idx = y.to(self.meshes.device).contiguous()

@@ -12,7 +12,9 @@ train step can be replayed from a hipGraph.  ``render`` / ``log_images`` draw
 with libcfsd's rasteriser (``rendering.py``) and write PNG files.  With a
 ``classifier:`` section the manager also carries the classifier stage
 (``classify.ClassifierStage``: MLP, LDA, QDA and the region LDAs / QDAs,
-``model_manager.py:403-573``) on libcfsd kernels; TensorBoard and the
+``model_manager.py:403-573``) on libcfsd kernels -- with
+``mlp_training_type: end2end`` the MLP is trained inside the VAE step
+(``engine.SDVAEEngine.attach_classifier_head``); TensorBoard and the
 ``LinearSVC`` are out of scope.  The reference's
 ``Tester`` over a resumed manager is ``evaluation.Tester``.
 """
@@ -120,7 +122,9 @@ class ModelManager(ClassifierStage):
             swap_bs=self.bs, seed=seed, device=self.device, precision=precision,
             swap_features=self._swap_features)
         self._latent_regions = self._compute_latent_regions()
-        self._init_classifiers(configurations, seed)  # nothing without a classifier: section
+        self._init_classifiers(configurations, seed, end2end=True)  # nothing without a classifier: section
+        # mlp_training_type: end2end -- the MLP's loss is a fifth term of the step (model_manager.py:295-318)
+        self._w_classifier_loss = float(self._classifier_params["mlp_loss_weight"]) if self._mlp_end2end else 0.0
         self._batch_diagonal_idx = [(self.bs + 1) * i for i in range(self.bs)]
         self._losses = None
         self.use_graph = use_graph
@@ -132,8 +136,11 @@ class ModelManager(ClassifierStage):
             from .dist import broadcast_parameters
             broadcast_parameters(self.engine.params.data, 0)
             self.engine.sync_shadow()
+            if self._mlp_end2end:  # the classifier is trained data-parallel too
+                broadcast_parameters(self.classifier_mlp.flat, 0)
         self.val_acc = torch.zeros(6, dtype=torch.float32, device=self.device)
         self.val_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.val_cls_acc = torch.zeros(3, dtype=torch.float32, device=self.device)
         # what render() draws: the side of the square image and its background
         # (a grey level or an (r, g, b) triple); evaluation.Tester sets both
         self.renderings_size = 256
@@ -188,7 +195,28 @@ class ModelManager(ClassifierStage):
                        batch_idx=b.batch_idx, bs=self.bs, n_batches=data.n_batches, perm=data.rows,
                        n_items=data.n_items, shuffle=data.shuffle)
         eng.load_batch(b, data)
-        eng.forward(b, train=False, acc=self.val_acc, finalize=True)
+        eng.forward(b, train=False, acc=self.val_acc, finalize=True, cls_acc=self.val_cls_acc)
+
+    def _prepare_end2end(self, data):
+        """The classifier head of the step (``mlp_training_type: end2end``):
+        attached once the class weights are known, and the data set's class
+        indices put on the device.  The reference fails on its ``None``
+        weights when ``set_class_conversions_and_weights`` has not run
+        (``train.py:48`` calls it before the loop); so does this."""
+        if self._class_weights is None:
+            raise RuntimeError("mlp_training_type: end2end needs the class weights: call "
+                               "set_class_conversions_and_weights(counts) before the first epoch")
+        eng = self.engine
+        if eng.head is None or eng.head.mlp is not self.classifier_mlp or eng.head.cw is not self._class_weights:
+            eng.attach_classifier_head(self.classifier_mlp, self._class_weights, self._w_classifier_loss)
+            self._steps = {}  # recorded steps hold the previous head's buffers
+        if getattr(data, "class_idx", None) is None and not hasattr(data, "labels"):
+            raise ValueError("mlp_training_type: end2end needs the data set's labels (ResidentData.labels, as "
+                             "data.load_mesh_dataset sets them, or ResidentData.class_idx)")
+        if hasattr(data, "labels") and (data.class_idx is None
+                                        or getattr(data, "class2idx", None) != self._class2idx_dict):
+            data.set_class_idx(self.class2idx([lab[0] for lab in data.labels]))
+            data.class2idx = dict(self._class2idx_dict)
 
     def run_epoch(self, data, train=True, record=None):
         """``ModelManager.run_epoch`` (model_manager.py:257-272): every batch
@@ -198,6 +226,10 @@ class ModelManager(ClassifierStage):
         b = self.engine.buffers(self.engine.step_rows)
         acc = self.engine.loss_acc if train else self.val_acc
         acc.zero_()
+        cacc = self.engine.cls_acc if train else self.val_cls_acc
+        if self._mlp_end2end:
+            self._prepare_end2end(data)
+            cacc.zero_()
         # writes made through ``net`` (a torch optimizer on its parameters,
         # net.load_state_dict) reach the fp32 master but not the bf16 shadow
         # the bf16 kernels read: refresh it once per epoch (one cast launch)
@@ -218,13 +250,20 @@ class ModelManager(ClassifierStage):
         if self.averager is not None and self.averager.world > 1:
             import torch.distributed as dist
             dist.all_reduce(acc)  # every rank's batches: sums and the batch count
+            if self._mlp_end2end:
+                dist.all_reduce(cacc)
         a = acc.cpu().numpy().astype(np.float64)
         if train:
             self.engine.check_health()  # a timed-out device wait invalidates the epoch: fail loudly
         n = max(a[5], 1.0)
+        cls, cls_acc, tot = 0.0, 0.0, a[4] / n
+        if self._mlp_end2end:  # the step's own total has the four VAE terms; the fifth is added here
+            c = cacc.cpu().numpy().astype(np.float64)
+            cls, cls_acc = c[0] / max(c[2], 1.0), c[1] / max(c[2], 1.0)
+            tot = tot + self._w_classifier_loss * cls
         self._losses = {"reconstruction": a[0] / n, "kl": a[1] / n, "latent_consistency": a[2] / n,
-                        "laplacian": a[3] / n, "classification": 0.0, "classification_acc": 0.0,
-                        "tot": a[4] / n}
+                        "laplacian": a[3] / n, "classification": cls, "classification_acc": cls_acc,
+                        "tot": tot}
         return dict(self._losses)
 
     def log_losses(self, writer, epoch, phase="train", losses=None):
@@ -385,7 +424,19 @@ class ModelManager(ClassifierStage):
         return ops.swap_features(data.meshes, idx, self.topology.region_mask, key, self.bs)
 
     def save_weights(self, checkpoint_dir, epoch):
-        return self.engine.save_weights(checkpoint_dir, epoch)
+        """``model_manager.py:682-688``: the model and its optimiser; with
+        ``mlp_training_type: end2end`` also ``mlp_classifier.pt`` (the
+        reference's format) and, beyond the reference, the classifier's Adam
+        state (``mlp_classifier_optimizer.pt``), so that a resumed run
+        continues bit for bit."""
+        name = self.engine.save_weights(checkpoint_dir, epoch)
+        if self._mlp_end2end:
+            mlp = self.classifier_mlp
+            torch.save({"model": {k: v.detach().cpu().clone() for k, v in mlp.state_dict().items()}},
+                       os.path.join(checkpoint_dir, "mlp_classifier.pt"))
+            torch.save({"exp_avg": mlp.exp_avg.cpu(), "exp_avg_sq": mlp.exp_avg_sq.cpu(), "step": mlp.step.cpu()},
+                       os.path.join(checkpoint_dir, "mlp_classifier_optimizer.pt"))
+        return name
 
     def resume(self, checkpoint_dir):
         """``ModelManager.resume`` (``model_manager.py:690-706``): the last
@@ -394,6 +445,12 @@ class ModelManager(ClassifierStage):
         epoch = self.engine.resume(checkpoint_dir)
         if self._classifier_params is not None:
             self.resume_classifiers(checkpoint_dir)
+            opt = os.path.join(checkpoint_dir, "mlp_classifier_optimizer.pt")
+            if self._mlp_end2end and os.path.exists(opt):
+                sd, mlp = torch.load(opt, map_location="cpu", weights_only=True), self.classifier_mlp
+                mlp.exp_avg.copy_(sd["exp_avg"])
+                mlp.exp_avg_sq.copy_(sd["exp_avg_sq"])
+                mlp.step.copy_(sd["step"])
         return epoch
 
 

@@ -1082,6 +1082,61 @@ def mlp_train_steps(z, label, class_weight, params, m, v, step, acc, dims, bs, n
          float(eps), float(weight_decay), stream_ptr())
 
 
+def mlp_head_step(z, batch_idx, label_table, class_weight, params, acc, dims, bs, row_stride=1, train=True, m=None,
+                  v=None, step=None, dlat=None, w_cls=1.0, dw_out=None, workspace=None, lr=1e-4, beta1=0.9,
+                  beta2=0.999, eps=1e-8, weight_decay=0.0):
+    """The MLP classifier as a head of the VAE step (``cfsd_mlp_head_step``,
+    ``mlp_training_type: end2end``, ``model_manager.py:295-318``): two
+    launches.  Row ``i < bs`` of the batch is row ``i * row_stride`` of ``z``
+    ``[rows, >= dims[0]]`` (``row_stride = bs + 1``: the diagonal of a swapped
+    group); its label is ``label_table[batch_idx[i]]`` (both int32).  ``acc``
+    ``[3]`` gains ``{loss, accuracy, 1}``.  ``train``: ``step`` += 1, ``w_cls *
+    dz`` is added to the first ``dims[0]`` columns of the same rows of ``dlat``
+    ``[rows, ld]``, and the parameters' gradient (times ``w_cls``) either
+    drives Adam in place (``m``, ``v`` given; ``dw_out`` optional) or is only
+    written to ``dw_out`` (``m = v = None``).  ``train=False``: loss and
+    accuracy only."""
+    dims, cdims = mlp_dims(dims)
+    bs, row_stride = int(bs), int(row_stride)
+    if not 1 <= bs <= MLP_MAX_BS:
+        raise ValueError(f"batch size {bs}: 1..{MLP_MAX_BS} are supported")
+    if row_stride < 1:
+        raise ValueError(f"row_stride {row_stride} < 1")
+    _need(z, None, name="z")
+    last = (bs - 1) * row_stride
+    if z.dim() != 2 or z.shape[1] < dims[0] or z.shape[0] <= last:
+        raise ValueError(f"z: shape {tuple(z.shape)}, expected [> {last}, >= {dims[0]}]")
+    _need(batch_idx, (bs,), torch.int32, "batch_idx")
+    _need(label_table, None, torch.int32, "label_table")
+    if label_table.dim() != 1 or label_table.numel() < 1:
+        raise ValueError(f"label_table: shape {tuple(label_table.shape)}, expected [N >= 1]")
+    _need(class_weight, (dims[-1],), name="class_weight")
+    n = mlp_param_count(dims)
+    _need(params, (n,), name="params")
+    _need(acc, (3,), name="acc")
+    nbytes, ld_dlat = 0, 0
+    if train:
+        if (m is None) != (v is None) or (m is None and dw_out is None):
+            raise ValueError("a train step takes m and v (Adam in place) or dw_out (the gradient only)")
+        if m is not None:
+            _need(m, (n,), name="m")
+            _need(v, (n,), name="v")
+        _need(step, (1,), torch.int32, "step")
+        _need(dlat, None, name="dlat")
+        if dlat.dim() != 2 or dlat.shape[1] < dims[0] or dlat.shape[0] <= last:
+            raise ValueError(f"dlat: shape {tuple(dlat.shape)}, expected [> {last}, >= {dims[0]}]")
+        ld_dlat = int(dlat.shape[1])
+        workspace, nbytes = _conv_ws(workspace, z.device, mlp_workspace(dims, bs))
+        if dw_out is not None:
+            _need(dw_out, (n,), name="dw_out")
+    call("cfsd_mlp_head_step", ptr(z), int(z.shape[1]), row_stride, ptr(batch_idx), ptr(label_table),
+         int(label_table.numel()), ptr(class_weight), ptr(params), ptr(m) if train else None,
+         ptr(v) if train else None, ptr(step) if train else None, ptr(acc), ptr(workspace) if train else None,
+         ctypes.c_size_t(nbytes), ptr(dw_out) if train else None, ptr(dlat) if train else None, ld_dlat,
+         float(w_cls), cdims, len(dims) - 1, bs, int(bool(train)), float(lr), float(beta1), float(beta2), float(eps),
+         float(weight_decay), stream_ptr())
+
+
 # ------------------------------------------------------------------ latent fitting
 NN_TILE = 16 # CFSD_NN_TILE: reference points per chunk of cfsd_nn_points (include/cfsd.h)
 

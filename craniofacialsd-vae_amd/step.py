@@ -17,6 +17,13 @@ Step anatomy (every launch on one stream; nothing synchronises with the host):
   reduce.  On one GPU Adam rides in that reduce (``cfsd_dw_reduce_batch_adam``);
 * ``part_c``: (data-parallel only) Adam, after the gradient all-reduce.
 
+With a classifier head attached (``SDVAEEngine.attach_classifier_head``, the
+reference's ``mlp_training_type: end2end``) two launches follow the latent head
+in ``part_a``: the classifier's forward / loss / backward into ``dlat``, and its
+parameters' gradient -- with Adam in the same launch on one GPU; data-parallel
+that gradient is a third bucket, all-reduced right after ``part_a``, and
+``part_c`` runs a second ``cfsd_adam_scaled`` for it.
+
 One graph per step whenever the collectives can be captured: on one GPU the
 three parts are ONE graph; data-parallel over RCCL the two bucket all-reduces
 are recorded INTO that graph (RCCL supports stream capture: the decoder /
@@ -64,12 +71,13 @@ class TrainStep:
     records the graphs; nothing executes while recording, so the k-th step
     of a captured runner equals the k-th step of an eager one, bit for bit."""
 
-    def __init__(self, engine, data, averager=None, acc=None):
+    def __init__(self, engine, data, averager=None, acc=None, cls_acc=None):
         self.eng = engine
         self.data = data
         self.avg = averager if (averager is not None and averager.active) else None
         self.b = engine.buffers(engine.step_rows)
         self.acc = engine.loss_acc if acc is None else acc
+        self.cls_acc = engine.cls_acc if cls_acc is None else cls_acc  # the classifier head's sums (if attached)
         self.graphs = None
         self.graph_multi = None
         # steps recorded into the multi-step graph run(k) replays (env: A/B)
@@ -97,7 +105,8 @@ class TrainStep:
                        n_batches=d.n_batches, perm=d.rows, n_items=d.n_items, shuffle=d.shuffle,
                        adam_step=eng.params.step)
         eng.load_batch(b, d)
-        eng.forward(b, train=True, acc=self.acc, finalize=False)
+        eng.forward(b, train=True, acc=self.acc, finalize=False, cls_acc=self.cls_acc,
+                    head_grad_only=self.avg is not None)
         eng.backward_head(b, split=self.avg is not None, fuse_adam=self.avg is None)
 
     def part_b(self):
@@ -106,9 +115,13 @@ class TrainStep:
     def part_c(self):
         if self.avg is not None:  # the 1/world averaging rides in the Adam launch
             self.eng.adam_step(grad_scale=1.0 / self.avg.world)
+            if self.eng.head is not None:
+                self.eng.head_adam_step(1.0 / self.avg.world)
 
     # ------------------------------------------------------------ buckets
     def _bucket_dec(self):
+        if self.eng.head is not None:  # the classifier's gradient: final since the head's second launch
+            self.avg.bucket_ready(self.eng.head.grad)
         self.avg.bucket_ready(self.eng.params.grad[self._split:])
 
     def _bucket_enc_and_finish(self):

@@ -20,7 +20,12 @@ With a ``classifier:`` section in the configuration the lead rank then runs
 the classifier stage (train.py:76-77, model_manager.py:448-504): the MLP
 classifier, LDA, QDA and the region LDAs / QDAs on the eval-mode latents, their
 files written next to the checkpoints and the validation accuracies to
-``<output>/classifiers.json``.  The ``LinearSVC`` is out of scope; latent
+``<output>/classifiers.json``.  With ``classifier.mlp_training_type: end2end``
+the MLP is trained inside the VAE step instead (its weighted cross-entropy
+times ``mlp_loss_weight`` joins the loss, model_manager.py:295-318;
+``classification`` / ``classification_acc`` are logged per epoch and
+``mlp_classifier.pt`` is written with the weights); the stage then only
+validates it.  The ``LinearSVC`` is out of scope; latent
 traversals and the rest of the reference's ``test.py`` run are ``evaluate.py``
 (``evaluation.Tester``).
 """
@@ -87,6 +92,9 @@ def main(argv=None):
         DD.barrier()
     train_set, val_set, test_set, norm = D.load_mesh_dataset(config["data"], bs, device, manager.template,
                                                              shard=(rank, world), seed=opts.seed)
+    if manager._classifier_params is not None:  # train.py:48: the classes and their weights, from the training set
+        from .classify import count_labels
+        manager.set_class_conversions_and_weights(count_labels(train_set.labels))
     start_epoch = manager.resume(checkpoint_dir) if opts.resume else 0
     epochs = opts.epochs if opts.epochs is not None else config["optimization"]["epochs"]
     save_every = config.get("logging_frequency", {}).get("save_weights", 100)
@@ -117,7 +125,7 @@ def main(argv=None):
         z = manager.encode(train_set.meshes)
         stats = manager.engine.latent_stats(z)
         torch.save({k: v.cpu() for k, v in stats.items()}, os.path.join(output_directory, "z_stats.pt"))
-        if "classifier" in config:
+        if manager._classifier_params is not None:
             acc = manager.train_and_validate_classifiers(train_set, val_set, writer, checkpoint_dir)
             with open(os.path.join(output_directory, "classifiers.json"), "w") as f:
                 json.dump({"validation_accuracy": acc, "classes": manager.class2idx_dict}, f)

@@ -861,6 +861,41 @@ int cfsd_mlp_train_steps(const float* z, const int32_t* label, const float* clas
                          int row0, int bs, int n_steps, int train, float lr, float beta1, float beta2,
                          float eps, float weight_decay, void* stream);
 
+/* cfsd_mlp_head_step (ABI 4.18): the MLP classifier as a head of the VAE step
+ * (classifier.mlp_training_type: end2end, model_manager.py:295-318): one step
+ * of cfsd_mlp_train_steps' two launches on bs <= 16 rows of the step's latent
+ * codes, whose loss gradient also flows back into the latent.
+ *   z: row i < bs at z + i * row_stride * ld_z (dims[0] floats).  row_stride =
+ *     bs + 1 takes the diagonal of a swapped bs x bs group
+ *     (model_manager.py:297), row_stride = 1 consecutive rows.
+ *   label of row i: label_table[batch_idx[i]] (batch_idx [bs] int32, the step's
+ *     base-mesh indices, clamped into [0, n_labels); label_table [n_labels]
+ *     int32 class indices, clamped into range).
+ *  1. one workgroup: forward, loss and accuracy exactly as documented for
+ *     cfsd_mlp_train_steps; acc[3] += {loss, acc, 1}.  train != 0: *step += 1,
+ *     the activation gradients, and one layer further dz_i = dy_0,i . W_0 (no
+ *     ReLU mask: the input is z):
+ *       dlat[i * row_stride * ld_dlat + c] += w_cls * dz_i[c],  c < dims[0],
+ *     a plain read-modify-write by the one thread that owns the element (in
+ *     stream order after cfsd_latent_fwd wrote dlat); every other element of
+ *     dlat keeps its bits.
+ *  2. (train != 0) one thread per parameter: w_cls times the gradient
+ *     cfsd_mlp_train_steps forms (the parameters see w_cls * loss), then
+ *       m, v != NULL: the cfsd_adam update in place (dw_out, may be NULL, also
+ *         receives the gradient);
+ *       m == v == NULL: the gradient only, into dw_out (required): the
+ *         data-parallel step, where cfsd_adam_scaled runs after the all-reduce.
+ * train == 0 (the validation pass, z = mu): launch 1's loss and accuracy only;
+ * nothing but acc is written (m, v, step, workspace, dlat, dw_out may be NULL).
+ * No atomics; two calls on the same inputs give the same bits.  workspace:
+ * cfsd_mlp_workspace(dims, n_layers, bs) bytes. */
+int cfsd_mlp_head_step(const float* z, int ld_z, int row_stride, const int32_t* batch_idx,
+                       const int32_t* label_table, int n_labels, const float* class_weight, float* params,
+                       float* m, float* v, int32_t* step, float* acc, void* workspace, size_t workspace_bytes,
+                       float* dw_out, float* dlat, int ld_dlat, float w_cls, const int* dims, int n_layers,
+                       int bs, int train, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
