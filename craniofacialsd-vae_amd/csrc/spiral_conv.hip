@@ -22,6 +22,7 @@
 #include "conv_vm32.h"
 #include "conv_coarse.h"
 #include "conv_lat.h"
+#include "conv_dispatch.h"
 
 namespace cfsd {
 
@@ -2171,6 +2172,76 @@ static int check_conv_args(const void* a, const void* b, const void* c, int batc
   return CFSD_OK;
 }
 
+// ---- argument checks shared by the entry points (all run before any launch)
+static int check_act(int act) {
+  if (act != CFSD_ACT_NONE && act != CFSD_ACT_ELU) return set_error(CFSD_EINVAL, "bad act %d", act);
+  return CFSD_OK;
+}
+// dW and db of one layer are reduced together, or both deferred
+static int check_dw_db(const float* dw, const float* db) {
+  if ((dw == nullptr) != (db == nullptr))
+    return set_error(CFSD_EINVAL, "dw and db must both be set (or both NULL: deferred)");
+  return CFSD_OK;
+}
+// the inverse tables are read as int4
+static int check_inv_aligned(const int32_t* table, const char* name) {
+  if ((uintptr_t)table & 15) return set_error(CFSD_EINVAL, "%s must be 16-B aligned", name);
+  return CFSD_OK;
+}
+static int check_flat_width(const char* who, int flat_width, int max_width = 16) {
+  if (flat_width <= 0 || flat_width > max_width || flat_width % 4)
+    return set_error(CFSD_EINVAL, "%s: flat_width %d not in {4, ..., %d}", who, flat_width, max_width);
+  return CFSD_OK;
+}
+static int check_workspace(size_t workspace_bytes, size_t need) {
+  if (workspace_bytes < need)
+    return set_error(CFSD_EWORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  return CFSD_OK;
+}
+static bool dt_ok(int dt) {
+  return (dt & ~(CFSD_VM | 0xf)) == 0 && (CFSD_DT_TYPE(dt) == CFSD_DT_F32 || CFSD_DT_TYPE(dt) == CFSD_DT_BF16);
+}
+static int check_dt(const char* who, int dt) {
+  if (!dt_ok(dt)) return set_error(CFSD_EINVAL, "%s: bad dtype %d", who, dt);
+  return CFSD_OK;
+}
+static int vm_of(int dt) { return (dt & CFSD_VM) != 0; }
+// dpre is addressed with 32-bit buffer offsets: `limit` is 2 GiB for the
+// list kernels, kAbsentRow where an offset doubles as the "absent" marker
+static int check_dpre_bound(int batch, int rows, int cout, int dpre_dt, long limit = 1L << 31) {
+  if ((long)batch * rows * cout * (CFSD_DT_TYPE(dpre_dt) == CFSD_DT_F32 ? 4L : 2L) >= limit)
+    return set_error(CFSD_EINVAL, "dpre of %d x %d x %d exceeds 32-bit buffer offsets", batch, rows, cout);
+  return CFSD_OK;
+}
+
+// ---- the shapes each kernel family instantiates (conv_dispatch.h); a new
+// shape of a family is added to its list here, and nowhere else
+using MfmaShapes = ShapeList<Shape<32, 32>, Shape<32, 64>, Shape<64, 32>, Shape<64, 64>>;
+// conv_fwd_in_mfma, conv_dw_in_mfma: the xyz input conv
+using XyzInShapes = ShapeList<Shape<1, 32>, Shape<2, 32>, Shape<3, 32>, Shape<1, 64>, Shape<2, 64>, Shape<3, 64>>;
+// conv_dw_in_small
+using InSmallShapes = ShapeList<Shape<3, 16>, Shape<3, 32>, Shape<3, 64>>;
+// conv_fwd_out_small
+using OutSmallShapes = ShapeList<Shape<16, 3>, Shape<32, 3>, Shape<64, 3>, Shape<32, 1>, Shape<32, 2>>;
+// conv_dx_out_small, conv_dw_out_small: the xyz output conv
+using XyzOutShapes = ShapeList<Shape<16, 3>, Shape<32, 3>, Shape<64, 3>>;
+// conv_bwd_out_mfma: fused dx + dW of a small-output layer
+using FusedSmallShapes =
+    ShapeList<Shape<32, 1>, Shape<32, 2>, Shape<32, 3>, Shape<64, 1>, Shape<64, 2>, Shape<64, 3>>;
+// conv_bwd_rowsub_pair
+using RowsubShapes = ShapeList<Shape<32, 32>, Shape<32, 64>>;
+// conv_bwd_lat_pair<CIN, COUT, CTW>, each shape with either CTW
+using LatPairShapes = ShapeList<Shape<32, 32>, Shape<64, 32>>;
+using LatPairCtws = IntList<1, 2>;
+// conv_dx_rowsub_gather<32, G>: G int4 groups per flat-list row
+using GatherGroups = IntList<1, 2, 3, 4>;
+// conv_fwd_in_swap<3, COUT>
+using SwapCouts = IntList<32, 64>;
+
+static bool mfma_shape(int cin, int cout) {
+  return (cin == 32 || cin == 64) && (cout == 32 || cout == 64);
+}
+
 // Persistent VALU kernels: one resident round, never more blocks than rows/64.
 template <typename K>
 static unsigned small_grid(K kernel, long rows) {
@@ -2222,8 +2293,8 @@ constexpr int kLatDwMax = kLatMaxRows;
 
 // coarse levels: slot groups in one workgroup, partials combined in LDS
 // (spiral_conv_coarse.hip)
-static int fwd_coarse(const float* x, int xvm, const int* idx, const float* w, const float* bias, float* y,
-                      int yvm, int vsrc, int rows, int batch, int cin, int cout, int act, hipStream_t st) {
+static coarse::FwdKsArgs fwd_ks_args(const float* x, int xvm, const int* idx, const float* w, const float* bias,
+                                     float* y, int yvm, int vsrc, int rows, int batch, int act) {
   coarse::FwdKsArgs a{};
   a.x = x;
   a.idx = idx;
@@ -2237,7 +2308,12 @@ static int fwd_coarse(const float* x, int xvm, const int* idx, const float* w, c
   a.xvm = xvm;
   a.yvm = yvm;
   a.elu = act == CFSD_ACT_ELU;
-  return coarse::launch_fwd_ks(a, cin, cout, st);
+  return a;
+}
+
+static int fwd_coarse(const float* x, int xvm, const int* idx, const float* w, const float* bias, float* y,
+                      int yvm, int vsrc, int rows, int batch, int cin, int cout, int act, hipStream_t st) {
+  return coarse::launch_fwd_ks(fwd_ks_args(x, xvm, idx, w, bias, y, yvm, vsrc, rows, batch, act), cin, cout, st);
 }
 
 extern "C" int cfsd_spiral_conv_fwd_up_supported(int batch, int rows, int seq, int cin, int cout) {
@@ -2252,25 +2328,16 @@ extern "C" int cfsd_spiral_conv_fwd_up(const float* xc, const int32_t* comp_col,
   int rc = check_conv_args(xc, idx, w, batch, n_coarse, rows, seq, cin, cout);
   if (rc) return rc;
   if (!comp_col || !comp_val || !y) return set_error(CFSD_EINVAL, "spiral_conv_fwd_up: null pointer");
-  if (act != CFSD_ACT_NONE && act != CFSD_ACT_ELU) return set_error(CFSD_EINVAL, "bad act %d", act);
+  if ((rc = check_act(act))) return rc;
   if (!coarse::fwd_up_supported((long)batch * rows, cin, cout))
     return set_error(CFSD_EINVAL, "spiral_conv_fwd_up: unsupported layer (%d x %d rows, %d -> %d)", batch, rows,
                      cin, cout);
-  coarse::FwdKsArgs a{};
-  a.x = xc;
-  a.idx = idx;
-  a.w = w;
-  a.bias = bias;
-  a.y = y;
+  // the conv reads the upsampled rows: its source level is its own
+  coarse::FwdKsArgs a = fwd_ks_args(xc, 0, idx, w, bias, y, 0, rows, rows, batch, act);
   a.yup = y_up;
   a.up_col = comp_col;
   a.up_val = comp_val;
-  a.vsrc = rows;
-  a.rows = rows;
-  a.batch = batch;
   a.n_coarse = n_coarse;
-  a.total_rows = (long)batch * rows;
-  a.elu = act == CFSD_ACT_ELU;
   return coarse::launch_fwd_ks(a, cin, cout, (hipStream_t)stream);
 }
 
@@ -2313,6 +2380,66 @@ extern "C" size_t cfsd_spiral_conv_workspace(int batch, int vsrc, int rows, int 
   return (a > b ? a : b) * sizeof(float);
 }
 
+// ---- small-channel forward, shared by cfsd_spiral_conv_fwd (fp32,
+// batch-major) and cfsd_spiral_conv_fwd_x (any storage and layout)
+template <int CS, int COUT, int ACT, typename TY>
+static int launch_fwd_in(const float* x, int xvm, const int* idx, const float* w, const float* bias, TY* y, int yvm,
+                         int vsrc, int rows, int batch, hipStream_t st) {
+  const long M = (long)batch * rows, tiles = (M + 31) / 32;
+  const unsigned gp = (unsigned)((tiles + 3) / 4 < 2048 ? (tiles + 3) / 4 : 2048);
+  hipLaunchKernelGGL((conv_fwd_in_mfma<CS, COUT, ACT, TY>), dim3(gp), dim3(256), 0, st, x, idx, w, bias, y, vsrc,
+                     rows, M, batch, xvm, yvm);
+  return launch_status("spiral_conv_fwd_in");
+}
+
+// The xyz input conv: fp32 x, y stored as y_dt.  kNoShape for another layer.
+static int fwd_xyz_in(const float* x, int xvm, const int* idx, const float* w, const float* bias, void* y, int y_dt,
+                      int yvm, int vsrc, int rows, int batch, int cin, int cout, int act, hipStream_t st) {
+  return for_shape(XyzInShapes{}, cin, cout, [&](auto s) {
+    using S = decltype(s);
+    return for_value(Acts{}, act, [&](auto a) {
+      return for_storage(y_dt, [&](auto t) {
+        using TY = typename decltype(t)::type;
+        return launch_fwd_in<S::cin, S::cout, decltype(a)::value, TY>(x, xvm, idx, w, bias, (TY*)y, yvm, vsrc, rows,
+                                                                      batch, st);
+      });
+    });
+  });
+}
+
+template <int CIN, int CO, int ACT, typename TX>
+static int launch_fwd_out_small(const TX* x, int xvm, const int* idx, const float* w, const float* bias, float* y,
+                                int yvm, int vsrc, int rows, int batch, hipStream_t st) {
+  const long M = (long)batch * rows;
+  auto k = conv_fwd_out_small<CIN, CO, ACT, TX>;
+  hipLaunchKernelGGL(k, dim3(small_grid(k, M)), dim3(256), 0, st, x, idx, w, bias, y, vsrc, rows, M, batch, xvm, yvm);
+  return launch_status("spiral_conv_fwd_out_small");
+}
+
+// A small-output conv: x stored as x_dt, fp32 y.  kNoShape for another layer.
+static int fwd_out_small(const void* x, int x_dt, int xvm, const int* idx, const float* w, const float* bias,
+                         float* y, int yvm, int vsrc, int rows, int batch, int cin, int cout, int act,
+                         hipStream_t st) {
+  return for_shape(OutSmallShapes{}, cin, cout, [&](auto s) {
+    using S = decltype(s);
+    return for_value(Acts{}, act, [&](auto a) {
+      return for_storage(x_dt, [&](auto t) {
+        using TX = typename decltype(t)::type;
+        return launch_fwd_out_small<S::cin, S::cout, decltype(a)::value, TX>((const TX*)x, xvm, idx, w, bias, y, yvm,
+                                                                             vsrc, rows, batch, st);
+      });
+    });
+  });
+}
+
+template <int ACT>
+static int launch_fwd_in_small(const float* x, const int* idx, const float* w, const float* bias, float* y,
+                               int vsrc, int rows, long M, hipStream_t st) {
+  hipLaunchKernelGGL((conv_fwd_in_small<3, 16, ACT>), dim3(row_grid(M)), dim3(256), 0, st, x, idx, w, bias, y, vsrc,
+                     rows, M);
+  return launch_status("spiral_conv_fwd_in_small");
+}
+
 extern "C" int cfsd_spiral_conv_fwd(const float* x, const int32_t* idx, const float* w,
                                     const float* bias, float* y, float* workspace,
                                     size_t workspace_bytes, int batch, int vsrc, int rows, int seq,
@@ -2322,54 +2449,29 @@ extern "C" int cfsd_spiral_conv_fwd(const float* x, const int32_t* idx, const fl
   if ((long)batch * rows >= (1L << 31) || (long)batch * vsrc >= (1L << 31))
     return set_error(CFSD_EINVAL, "spiral_conv_fwd: batch*rows must be < 2^31");
   if (!y) return set_error(CFSD_EINVAL, "null y");
-  if (act != CFSD_ACT_NONE && act != CFSD_ACT_ELU) return set_error(CFSD_EINVAL, "bad act %d", act);
+  if ((rc = check_act(act))) return rc;
   hipStream_t st = (hipStream_t)stream;
   const long M = (long)batch * rows;
   const size_t wsf = workspace ? workspace_bytes / sizeof(float) : 0;
-#define FWD(CIN_, COUT_)                                                                         \
-  if (cin == CIN_ && cout == COUT_)                                                              \
-    return act == CFSD_ACT_ELU                                                                   \
-               ? dispatch_fwd_mfma<CIN_, COUT_, CFSD_ACT_ELU>(x, idx, w, bias, y, workspace, wsf, \
-                                                              vsrc, rows, M, st)                 \
-               : dispatch_fwd_mfma<CIN_, COUT_, CFSD_ACT_NONE>(x, idx, w, bias, y, workspace,    \
-                                                               wsf, vsrc, rows, M, st);
-  FWD(32, 32) FWD(32, 64) FWD(64, 32) FWD(64, 64)
-#undef FWD
-  if (cin <= 3 && (cout == 32 || cout == 64)) {
-    const long tiles = (M + 31) / 32;
-    const unsigned gp = (unsigned)((tiles + 3) / 4 < 2048 ? (tiles + 3) / 4 : 2048);
-#define FIN(CS_, CO_)                                                                            \
-  if (cin == CS_ && cout == CO_) {                                                               \
-    if (act == CFSD_ACT_ELU)                                                                     \
-      hipLaunchKernelGGL((conv_fwd_in_mfma<CS_, CO_, CFSD_ACT_ELU>), dim3(gp), dim3(256), 0, st,  \
-                         x, idx, w, bias, y, vsrc, rows, M, batch, 0, 0);                        \
-    else                                                                                         \
-      hipLaunchKernelGGL((conv_fwd_in_mfma<CS_, CO_, CFSD_ACT_NONE>), dim3(gp), dim3(256), 0, st, \
-                         x, idx, w, bias, y, vsrc, rows, M, batch, 0, 0);                        \
-    return launch_status("spiral_conv_fwd_in");                                                  \
+  rc = for_shape(MfmaShapes{}, cin, cout, [&](auto s) {
+    using S = decltype(s);
+    return for_value(Acts{}, act, [&](auto a) {
+      return dispatch_fwd_mfma<S::cin, S::cout, decltype(a)::value>(x, idx, w, bias, y, workspace, wsf, vsrc, rows, M,
+                                                                    st);
+    });
+  });
+  if (rc != kNoShape) return rc;
+  rc = fwd_xyz_in(x, 0, idx, w, bias, y, CFSD_DT_F32, 0, vsrc, rows, batch, cin, cout, act, st);
+  if (rc != kNoShape) return rc;
+  if (cin == 3 && cout == 16)
+    return for_value(Acts{}, act, [&](auto a) {
+      return launch_fwd_in_small<decltype(a)::value>(x, idx, w, bias, y, vsrc, rows, M, st);
+    });
+  // only the three xyz output shapes here: 32 -> 1 and 32 -> 2 are taken by cfsd_spiral_conv_fwd_x alone
+  if (cout == 3) {
+    rc = fwd_out_small(x, CFSD_DT_F32, 0, idx, w, bias, y, 0, vsrc, rows, batch, cin, cout, act, st);
+    if (rc != kNoShape) return rc;
   }
-    FIN(1, 32) FIN(2, 32) FIN(3, 32) FIN(1, 64) FIN(2, 64) FIN(3, 64)
-#undef FIN
-  }
-#define FWD_SMALL(KERNEL, A_, B_, ...)                                                           \
-  if (cin == A_ && cout == B_) {                                                                 \
-    if (act == CFSD_ACT_ELU) {                                                                   \
-      auto k = KERNEL<A_, B_, CFSD_ACT_ELU>;                                                     \
-      hipLaunchKernelGGL(k, dim3(GRID(k)), dim3(256), 0, st, x, idx, w, bias, y, vsrc, rows, M __VA_ARGS__); \
-    } else {                                                                                     \
-      auto k = KERNEL<A_, B_, CFSD_ACT_NONE>;                                                    \
-      hipLaunchKernelGGL(k, dim3(GRID(k)), dim3(256), 0, st, x, idx, w, bias, y, vsrc, rows, M __VA_ARGS__); \
-    }                                                                                            \
-    return launch_status("spiral_conv_fwd_small");                                               \
-  }
-#define GRID(k) row_grid(M)
-  FWD_SMALL(conv_fwd_in_small, 3, 16)
-#undef GRID
-#define GRID(k) small_grid(k, M)
-  FWD_SMALL(conv_fwd_out_small, 16, 3, , batch, 0, 0) FWD_SMALL(conv_fwd_out_small, 32, 3, , batch, 0, 0)
-  FWD_SMALL(conv_fwd_out_small, 64, 3, , batch, 0, 0)
-#undef GRID
-#undef FWD_SMALL
   return set_error(CFSD_EINVAL, "spiral_conv_fwd: unsupported channels %d -> %d", cin, cout);
 }
 
@@ -2450,6 +2552,15 @@ static int dispatch_dx_mfma(const float* dpre, const int* inv_ptr, const int* in
                                       rows, M, st);
 }
 
+template <int CIN, int CO>
+static int launch_dx_out_small(const float* dpre, const int* inv_ptr, const int* inv_row, const int* inv_head,
+                               const float* w, const float* elu_y, float* dx, int vsrc, int rows, long M,
+                               hipStream_t st) {
+  hipLaunchKernelGGL((conv_dx_out_small<CIN, CO>), dim3(row_grid(M)), dim3(256), 0, st, dpre, inv_ptr, inv_row,
+                     (const int4*)inv_head, w, elu_y, dx, vsrc, rows, M);
+  return launch_status("spiral_conv_bwd_data_small");
+}
+
 extern "C" int cfsd_spiral_conv_bwd_data(const float* dpre, const int32_t* inv_ptr,
                                          const int32_t* inv_row, const int32_t* inv_head,
                                          const float* w, const float* elu_y, float* dx,
@@ -2459,27 +2570,22 @@ extern "C" int cfsd_spiral_conv_bwd_data(const float* dpre, const int32_t* inv_p
   int rc = check_conv_args(dpre, inv_ptr, inv_row, batch, vsrc, rows, seq, cin, cout);
   if (rc) return rc;
   if (!w || !dx || !inv_head) return set_error(CFSD_EINVAL, "null w/dx/inv_head");
-  if ((uintptr_t)inv_head & 15) return set_error(CFSD_EINVAL, "inv_head must be 16-B aligned");
-  if ((long)batch * rows * cout * (long)sizeof(float) >= (1L << 31))
-    return set_error(CFSD_EINVAL, "dpre larger than 2 GiB (32-bit buffer offsets)");
+  if ((rc = check_inv_aligned(inv_head, "inv_head"))) return rc;
+  if ((rc = check_dpre_bound(batch, rows, cout, CFSD_DT_F32))) return rc;
   hipStream_t st = (hipStream_t)stream;
   const long M = (long)batch * vsrc;
   const size_t wsf = workspace ? workspace_bytes / sizeof(float) : 0;
-#define DXM(CIN_, COUT_)                                                                       \
-  if (cin == CIN_ && cout == COUT_)                                                            \
-    return dispatch_dx_mfma<CIN_, COUT_>(dpre, inv_ptr, inv_row, inv_head, w, elu_y, dx,       \
-                                         workspace, wsf, vsrc, rows, M, st);
-  DXM(32, 32) DXM(32, 64) DXM(64, 32) DXM(64, 64)
-#undef DXM
-#define DXS(CIN_, CO_)                                                                          \
-  if (cin == CIN_ && cout == CO_) {                                                             \
-    auto k = conv_dx_out_small<CIN_, CO_>;                                                      \
-    hipLaunchKernelGGL(k, dim3(row_grid(M)), dim3(256), 0, st,                                  \
-                       dpre, inv_ptr, inv_row, (const int4*)inv_head, w, elu_y, dx, vsrc, rows, M); \
-    return launch_status("spiral_conv_bwd_data_small");                                        \
-  }
-  DXS(16, 3) DXS(32, 3) DXS(64, 3)
-#undef DXS
+  rc = for_shape(MfmaShapes{}, cin, cout, [&](auto s) {
+    using S = decltype(s);
+    return dispatch_dx_mfma<S::cin, S::cout>(dpre, inv_ptr, inv_row, inv_head, w, elu_y, dx, workspace, wsf, vsrc,
+                                             rows, M, st);
+  });
+  if (rc != kNoShape) return rc;
+  rc = for_shape(XyzOutShapes{}, cin, cout, [&](auto s) {
+    using S = decltype(s);
+    return launch_dx_out_small<S::cin, S::cout>(dpre, inv_ptr, inv_row, inv_head, w, elu_y, dx, vsrc, rows, M, st);
+  });
+  if (rc != kNoShape) return rc;
   return set_error(CFSD_EINVAL, "spiral_conv_bwd_data: unsupported channels %d -> %d", cin, cout);
 }
 
@@ -2499,13 +2605,11 @@ size_t dw_units(int cin, int cout) { return (size_t)kSeq * (cout / 32) * (cin / 
 // one resident round.
 int dw_mfma_slabs(int cin, int cout, int gx) {
   int cap = gx;
-#define CAP(CIN_, COUT_)                                                                         \
-  if (cin == CIN_ && cout == COUT_) {                                                            \
-    using C = DwCfg<CIN_, COUT_>;                                                                \
-    cap = resident_blocks_of(conv_dw_mfma<CIN_, COUT_>, C::THREADS, C::LDS_FLOATS * sizeof(float)); \
-  }
-  CAP(32, 32) CAP(32, 64) CAP(64, 32) CAP(64, 64)
-#undef CAP
+  for_shape(MfmaShapes{}, cin, cout, [&](auto s) {
+    using S = decltype(s);
+    using C = DwCfg<S::cin, S::cout>;
+    return cap = resident_blocks_of(conv_dw_mfma<S::cin, S::cout>, C::THREADS, C::LDS_FLOATS * sizeof(float));
+  });
   return gx < cap ? gx : cap;
 }
 
@@ -2576,6 +2680,74 @@ extern "C" size_t cfsd_spiral_conv_bwd_weight_workspace(int batch, int rows, int
   return dw_geom(batch, rows, cin, cout).ws_floats * sizeof(float);
 }
 
+// ---- reduce epilogues: the slabs a weight-gradient launch left in the
+// workspace, summed into dw / db
+// MFMA-shaped layers: 1024-float unit slabs, db partials behind them
+static int reduce_dw_units(bool deferred, int cin, int cout, float* workspace, float* ws_db, float* dw, float* db,
+                           int n_slabs, hipStream_t st) {
+  if (deferred) return CFSD_OK;  // cfsd_dw_reduce_batch sums the slabs later
+  const int n_el = cout * kSeq * cin + cout;
+  const int rc = for_shape(MfmaShapes{}, cin, cout, [&](auto s) {
+    using S = decltype(s);
+    hipLaunchKernelGGL((conv_dw_reduce<S::cin, S::cout>), dim3((unsigned)((n_el + 63) / 64)), dim3(1024), 0, st,
+                       workspace, ws_db, dw, db, n_slabs);
+    return launch_status("spiral_conv_bwd_weight_reduce");
+  });
+  return rc != kNoShape ? rc : set_error(CFSD_EINVAL, "dw reduce: unsupported channels %d -> %d", cin, cout);
+}
+
+// every other layer: n_slabs plain slabs of [cout x 9 cin | cout] floats
+static int reduce_slabs(bool deferred, int cin, int cout, float* workspace, int n_slabs, float* dw, float* db,
+                        hipStream_t st) {
+  if (deferred) return CFSD_OK;
+  const int n_el = cout * kSeq * cin + cout;
+  hipLaunchKernelGGL(slab_reduce, dim3((unsigned)((n_el + 63) / 64)), dim3(1024), 0, st, workspace, n_slabs, n_el, dw,
+                     cout * kSeq * cin, db);
+  return launch_status("spiral_conv_slab_reduce");
+}
+
+template <int CIN, int COUT>
+static int launch_dw_lat(const float* x, int xvm, const int* idx, const float* dpre, int dpvm, float* workspace,
+                         float* ws_db, const DwGeom& g, int vsrc, int rows, int batch, hipStream_t st) {
+  const long tasks = lat_tasks(g.gx, dw_units(CIN, COUT));
+  hipLaunchKernelGGL((conv_dw_lat<CIN, COUT>), dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, st, x, idx, dpre,
+                     workspace, ws_db, vsrc, rows, batch * rows, g.rchunk, g.gx, batch, xvm, dpvm);
+  return launch_status("spiral_conv_bwd_weight_lat");
+}
+
+template <int CIN, int COUT>
+static int launch_dw_mfma(const float* x, int xvm, const int* idx, const float* dpre, int dpvm, float* workspace,
+                          float* ws_db, int n_slabs, int vsrc, int rows, int batch, hipStream_t st) {
+  using C = DwCfg<CIN, COUT>;
+  hipLaunchKernelGGL((conv_dw_mfma<CIN, COUT>), dim3(n_slabs), dim3(C::THREADS), C::LDS_FLOATS * sizeof(float), st, x,
+                     idx, dpre, workspace, ws_db, vsrc, rows, (long)batch * rows, batch, xvm, dpvm);
+  return launch_status("spiral_conv_bwd_weight");
+}
+
+// conv_dw_in_small / conv_dw_out_small: fp32, batch-major
+template <typename K>
+static int launch_dw_small(K kernel, int gx, const float* x, const int* idx, const float* dpre, float* workspace,
+                           int vsrc, int rows, long M, hipStream_t st) {
+  hipLaunchKernelGGL(kernel, dim3(gx), dim3(256), 0, st, x, idx, dpre, workspace, vsrc, rows, M);
+  return launch_status("spiral_conv_bwd_weight_small");
+}
+
+// dW slabs of the xyz input conv: fp32 x, dpre stored as dpre_dt; shared by
+// cfsd_spiral_conv_bwd_weight and cfsd_spiral_conv_bwd_weight_x.  kNoShape
+// for another layer.
+static int dw_xyz_in(const float* x, int xvm, const int* idx, const void* dpre, int dpre_dt, int dpvm,
+                     float* workspace, int gx, int vsrc, int rows, int batch, int cin, int cout, hipStream_t st) {
+  return for_shape(XyzInShapes{}, cin, cout, [&](auto s) {
+    using S = decltype(s);
+    return for_storage(dpre_dt, [&](auto t) {
+      using TD = typename decltype(t)::type;
+      hipLaunchKernelGGL((conv_dw_in_mfma<S::cin, S::cout, TD>), dim3(gx), dim3(256), 0, st, x, idx, (const TD*)dpre,
+                         workspace, vsrc, rows, (long)batch * rows, batch, xvm, dpvm);
+      return launch_status("spiral_conv_bwd_weight_in");
+    });
+  });
+}
+
 constexpr int kDwVm32 = 1;  // 32 -> 32 with vertex-major x and dpre: vm32::conv_dw_vm32
 // The fp32 weight gradient takes vm32::conv_dw_vm32 (its slabs: cfsd_dw_slabs.fused == 3)
 static bool dw_vm32_path(int xvm, int dpvm, int cin, int cout, int batch) {
@@ -2588,84 +2760,57 @@ static int dw_f32(const float* x, int xvm, const int32_t* idx, const float* dpre
                   int cin, int cout, hipStream_t st) {
   int rc = CFSD_OK;
   if (!workspace) return set_error(CFSD_EINVAL, "null workspace");
-  if ((dw == nullptr) != (db == nullptr))
-    return set_error(CFSD_EINVAL, "dw and db must both be set (or both NULL: deferred)");
+  if ((rc = check_dw_db(dw, db))) return rc;
   const bool deferred = dw == nullptr;
   DwGeom g = dw_geom(batch, rows, cin, cout);
   if (g.kind == kDwNone)
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight: unsupported channels %d -> %d", cin, cout);
-  if (workspace_bytes < g.ws_floats * sizeof(float))
-    return set_error(CFSD_EWORKSPACE, "workspace %zu < %zu bytes", workspace_bytes,
-                     g.ws_floats * sizeof(float));
+  if ((rc = check_workspace(workspace_bytes, g.ws_floats * sizeof(float)))) return rc;
   if ((xvm || dpvm) && g.kind != kDwLat && g.kind != kDwMfma)
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight: vertex-major operands need 32/64 channels");
   if ((long)batch * vsrc * cin >= (1L << 31))
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight: x has >= 2^31 elements (32-bit offsets)");
   const long M = (long)batch * rows;
-  const int n_el = cout * kSeq * cin + cout;
-  const dim3 rg((unsigned)((n_el + 63) / 64));
-  if (g.kind == kDwLat) {
+  if (g.kind == kDwLat || g.kind == kDwMfma) {
     float* ws_db = workspace + (size_t)g.gx * dw_units(cin, cout) * 1024;
-    const long tasks = lat_tasks(g.gx, dw_units(cin, cout));
-#define DWL(CIN_, COUT_)                                                                        \
-  if (cin == CIN_ && cout == COUT_) {                                                           \
-    hipLaunchKernelGGL((conv_dw_lat<CIN_, COUT_>), dim3((unsigned)((tasks + 3) / 4)), dim3(256), \
-                       0, st, x, idx, dpre, workspace, ws_db, vsrc, rows, (int)M, g.rchunk,      \
-                       g.gx, batch, xvm, dpvm);                                                 \
-    rc = launch_status("spiral_conv_bwd_weight_lat");                                           \
-    if (rc || deferred) return rc;                                                              \
-    hipLaunchKernelGGL((conv_dw_reduce<CIN_, COUT_>), rg, dim3(1024), 0, st, workspace, ws_db,  \
-                       dw, db, lat_slabs(g.gx));                                                \
-    return launch_status("spiral_conv_bwd_weight_reduce");                                      \
-  }
-    DWL(32, 32) DWL(32, 64) DWL(64, 32) DWL(64, 64)
-#undef DWL
-  }
-  if (g.kind == kDwMfma) {
-    float* ws_db = workspace + (size_t)g.gx * dw_units(cin, cout) * 1024;
-    int nslab = g.gx;
-#define DWM(CIN_, COUT_)                                                                        \
-  if (cin == CIN_ && cout == COUT_) {                                                           \
-    using C = DwCfg<CIN_, COUT_>;                                                               \
-    auto k = conv_dw_mfma<CIN_, COUT_>;                                                         \
-    if (dw_vm32_path(xvm, dpvm, cin, cout, batch)) {                                            \
-      nslab = vm32::dw_slabs(batch, rows, g.gx);                                                \
-      rc = vm32::launch_dw(x, idx, dpre, workspace, ws_db, nslab, vsrc, rows, batch, st);        \
-    } else {                                                                                    \
-      nslab = dw_mfma_slabs(cin, cout, g.gx);                                                   \
-      hipLaunchKernelGGL(k, dim3(nslab), dim3(C::THREADS), C::LDS_FLOATS * sizeof(float), st, x, \
-                         idx, dpre, workspace, ws_db, vsrc, rows, M, batch, xvm, dpvm);         \
-      rc = launch_status("spiral_conv_bwd_weight");                                             \
-    }                                                                                           \
-    if (rc || deferred) return rc;                                                              \
-    hipLaunchKernelGGL((conv_dw_reduce<CIN_, COUT_>), rg, dim3(1024), 0, st, workspace, ws_db,  \
-                       dw, db, nslab);                                                          \
-    return launch_status("spiral_conv_bwd_weight_reduce");                                      \
-  }
-    DWM(32, 32) DWM(32, 64) DWM(64, 32) DWM(64, 64)
-#undef DWM
-  }
-#define DWS(KERNEL, A_, B_, ...)                                                                  \
-  if (cin == A_ && cout == B_) {                                                                  \
-    hipLaunchKernelGGL((KERNEL<A_, B_>), dim3(g.gx), dim3(256), 0, st, x, idx, dpre, workspace,   \
-                       vsrc, rows, M __VA_ARGS__);                                                \
-    rc = launch_status("spiral_conv_bwd_weight_small");                                           \
-    if (rc || deferred) return rc;                                                                \
-    hipLaunchKernelGGL(slab_reduce, rg, dim3(1024), 0, st, workspace, g.gx, n_el, dw,             \
-                       cout * kSeq * cin, db);                                                    \
-    return launch_status("spiral_conv_bwd_weight_small_reduce");                                  \
+    int n_slabs;
+    if (g.kind == kDwLat) {
+      n_slabs = lat_slabs(g.gx);
+      rc = for_shape(MfmaShapes{}, cin, cout, [&](auto s) {
+        using S = decltype(s);
+        return launch_dw_lat<S::cin, S::cout>(x, xvm, idx, dpre, dpvm, workspace, ws_db, g, vsrc, rows, batch, st);
+      });
+    } else if (dw_vm32_path(xvm, dpvm, cin, cout, batch)) {
+      n_slabs = vm32::dw_slabs(batch, rows, g.gx);
+      rc = vm32::launch_dw(x, idx, dpre, workspace, ws_db, n_slabs, vsrc, rows, batch, st);
+    } else {
+      n_slabs = dw_mfma_slabs(cin, cout, g.gx);
+      rc = for_shape(MfmaShapes{}, cin, cout, [&](auto s) {
+        using S = decltype(s);
+        return launch_dw_mfma<S::cin, S::cout>(x, xvm, idx, dpre, dpvm, workspace, ws_db, n_slabs, vsrc, rows, batch,
+                                               st);
+      });
+    }
+    if (rc) return rc;  // (never kNoShape: dw_geom gives these kinds to the MFMA shapes only)
+    return reduce_dw_units(deferred, cin, cout, workspace, ws_db, dw, db, n_slabs, st);
   }
   if (g.kind == kDwInMfma) {
-    DWS(conv_dw_in_mfma, 3, 32, , batch, 0, 0) DWS(conv_dw_in_mfma, 3, 64, , batch, 0, 0)
-    DWS(conv_dw_in_mfma, 2, 32, , batch, 0, 0) DWS(conv_dw_in_mfma, 2, 64, , batch, 0, 0)
-    DWS(conv_dw_in_mfma, 1, 32, , batch, 0, 0) DWS(conv_dw_in_mfma, 1, 64, , batch, 0, 0)
+    rc = dw_xyz_in(x, 0, idx, dpre, CFSD_DT_F32, 0, workspace, g.gx, vsrc, rows, batch, cin, cout, st);
   } else if (g.kind == kDwInSmall) {
-    DWS(conv_dw_in_small, 3, 16) DWS(conv_dw_in_small, 3, 32) DWS(conv_dw_in_small, 3, 64)
+    rc = for_shape(InSmallShapes{}, cin, cout, [&](auto s) {
+      using S = decltype(s);
+      return launch_dw_small(conv_dw_in_small<S::cin, S::cout>, g.gx, x, idx, dpre, workspace, vsrc, rows, M, st);
+    });
   } else {
-    DWS(conv_dw_out_small, 16, 3) DWS(conv_dw_out_small, 32, 3) DWS(conv_dw_out_small, 64, 3)
+    rc = for_shape(XyzOutShapes{}, cin, cout, [&](auto s) {
+      using S = decltype(s);
+      return launch_dw_small(conv_dw_out_small<S::cin, S::cout>, g.gx, x, idx, dpre, workspace, vsrc, rows, M, st);
+    });
   }
-#undef DWS
-  return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight: unsupported channels %d -> %d", cin, cout);
+  if (rc == kNoShape)
+    return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight: unsupported channels %d -> %d", cin, cout);
+  if (rc) return rc;
+  return reduce_slabs(deferred, cin, cout, workspace, g.gx, dw, db, st);
 }
 
 extern "C" int cfsd_spiral_conv_bwd_weight(const float* x, const int32_t* idx, const float* dpre,
@@ -2725,6 +2870,29 @@ extern "C" size_t cfsd_spiral_conv_bwd_workspace(int batch, int vsrc, int rows, 
   return a > b ? a : b;
 }
 
+// Fused dx + dW slabs of a small-output layer, then the slab reduce; x, elu_y
+// and dx share x's storage and layout (x_dt), dpre is fp32.  Shared by
+// cfsd_spiral_conv_bwd and cfsd_spiral_conv_bwd_x.  kNoShape for another layer.
+static int bwd_fused_small(const void* x, int x_dt, const float* dpre, int dpvm,
+                           const int32_t* inv_ptr, const int32_t* inv_row, const int32_t* inv_head, const float* w,
+                           const void* elu_y, void* dx, float* dw, float* db, float* workspace, int batch, int vsrc,
+                           int rows, int cin, int cout, hipStream_t st) {
+  const long Ms = (long)batch * vsrc;
+  const int gx = fused_small_gx(Ms);
+  const int rc = for_shape(FusedSmallShapes{}, cin, cout, [&](auto s) {
+    using S = decltype(s);
+    return for_storage(x_dt, [&](auto t) {
+      using TX = typename decltype(t)::type;
+      hipLaunchKernelGGL((conv_bwd_out_mfma<S::cin, S::cout, TX>), dim3(gx), dim3(256), 0, st, dpre, inv_ptr, inv_row,
+                         (const int4*)inv_head, w, (const TX*)elu_y, (const TX*)x, (TX*)dx, workspace, vsrc, rows, Ms,
+                         batch, vm_of(x_dt), dpvm);
+      return launch_status("spiral_conv_bwd_small");
+    });
+  });
+  if (rc) return rc;
+  return reduce_slabs(!dw, cin, cout, workspace, gx, dw, db, st);
+}
+
 extern "C" int cfsd_spiral_conv_bwd(const float* x, const int32_t* idx, const float* dpre,
                                     const int32_t* inv_ptr, const int32_t* inv_row,
                                     const int32_t* inv_head, const float* w, const float* elu_y,
@@ -2735,14 +2903,11 @@ extern "C" int cfsd_spiral_conv_bwd(const float* x, const int32_t* idx, const fl
   if (rc) return rc;
   if (!inv_ptr || !inv_row || !inv_head || !w || !workspace)
     return set_error(CFSD_EINVAL, "spiral_conv_bwd: null inverse table / w / workspace");
-  if ((uintptr_t)inv_head & 15) return set_error(CFSD_EINVAL, "inv_head must be 16-B aligned");
-  if ((long)batch * rows * cout * (long)sizeof(float) >= (1L << 31))
-    return set_error(CFSD_EINVAL, "dpre larger than 2 GiB (32-bit buffer offsets)");
-  if ((dw == nullptr) != (db == nullptr))
-    return set_error(CFSD_EINVAL, "dw and db must both be set (or both NULL: deferred)");
-  const size_t need = cfsd_spiral_conv_bwd_workspace(batch, vsrc, rows, seq, cin, cout);
-  if (workspace_bytes < need)
-    return set_error(CFSD_EWORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  if ((rc = check_inv_aligned(inv_head, "inv_head"))) return rc;
+  if ((rc = check_dpre_bound(batch, rows, cout, CFSD_DT_F32))) return rc;
+  if ((rc = check_dw_db(dw, db))) return rc;
+  if ((rc = check_workspace(workspace_bytes, cfsd_spiral_conv_bwd_workspace(batch, vsrc, rows, seq, cin, cout))))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   if (dx && bwd_ks_paired(batch, vsrc, rows, cin, cout)) {
     const DwGeom g = dw_geom(batch, rows, cin, cout);
@@ -2751,16 +2916,8 @@ extern "C" int cfsd_spiral_conv_bwd(const float* x, const int32_t* idx, const fl
                              (long)batch * vsrc};
     const DwLatArgs d{x, idx, dpre, workspace, ws_db, vsrc, rows, batch * rows, g.rchunk, g.gx, 0, batch, 0, 0};
     rc = coarse::launch_bwd_ks_pair(a, d, lat_tasks(g.gx, dw_units(cin, cout)), cin, cout, st);
-    if (rc || !dw) return rc;
-    const int n_el = cout * kSeq * cin + cout;
-#define KSR(CIN_, COUT_)                                                                             \
-  if (cin == CIN_ && cout == COUT_) {                                                                \
-    hipLaunchKernelGGL((conv_dw_reduce<CIN_, COUT_>), dim3((unsigned)((n_el + 63) / 64)), dim3(1024), 0, st, \
-                       workspace, ws_db, dw, db, lat_slabs(g.gx));                                   \
-    return launch_status("spiral_conv_bwd_weight_reduce");                                           \
-  }
-    KSR(32, 32) KSR(32, 64) KSR(64, 32) KSR(64, 64)
-#undef KSR
+    if (rc) return rc;
+    return reduce_dw_units(!dw, cin, cout, workspace, ws_db, dw, db, lat_slabs(g.gx), st);
   }
   if (dx && bwd_paired(batch, vsrc, rows, cin, cout)) {
     const DwGeom g = dw_geom(batch, rows, cin, cout);
@@ -2773,19 +2930,16 @@ extern "C" int cfsd_spiral_conv_bwd(const float* x, const int32_t* idx, const fl
     const int ctw = dx_lat_ctw(cin, cout, M);
     a.nb = (int)(((M + 15) / 16 * (cin / 16 / ctw) + 3) / 4);
     const dim3 grid((unsigned)(a.nb + d.nb));
-    const int n_el = cout * kSeq * cin + cout;
-#define PAIR(CIN_, COUT_, CTW_)                                                                 \
-  if (cin == CIN_ && cout == COUT_ && ctw == CTW_) {                                            \
-    hipLaunchKernelGGL((conv_bwd_lat_pair<CIN_, COUT_, CTW_>), grid, dim3(256), 0, st, a, d);    \
-    rc = launch_status("spiral_conv_bwd_lat_pair");                                             \
-    if (rc || !dw) return rc;                                                                   \
-    hipLaunchKernelGGL((conv_dw_reduce<CIN_, COUT_>), dim3((unsigned)((n_el + 63) / 64)),        \
-                       dim3(1024), 0, st, workspace, ws_db, dw, db, lat_slabs(g.gx));           \
-    return launch_status("spiral_conv_bwd_weight_reduce");                                      \
-  }
-    PAIR(32, 32, 1) PAIR(32, 32, 2) PAIR(64, 32, 1) PAIR(64, 32, 2)
-#undef PAIR
-    return set_error(CFSD_EINVAL, "spiral_conv_bwd: unsupported channels %d -> %d", cin, cout);
+    rc = for_shape(LatPairShapes{}, cin, cout, [&](auto s) {
+      using S = decltype(s);
+      return for_value(LatPairCtws{}, ctw, [&](auto c) {
+        hipLaunchKernelGGL((conv_bwd_lat_pair<S::cin, S::cout, decltype(c)::value>), grid, dim3(256), 0, st, a, d);
+        return launch_status("spiral_conv_bwd_lat_pair");
+      });
+    });
+    if (rc == kNoShape) return set_error(CFSD_EINVAL, "spiral_conv_bwd: unsupported channels %d -> %d", cin, cout);
+    if (rc) return rc;
+    return reduce_dw_units(!dw, cin, cout, workspace, ws_db, dw, db, lat_slabs(g.gx), st);
   }
   if (!fused_small(cin, cout)) {
     if (dx) {
@@ -2796,22 +2950,9 @@ extern "C" int cfsd_spiral_conv_bwd(const float* x, const int32_t* idx, const fl
     return cfsd_spiral_conv_bwd_weight(x, idx, dpre, dw, db, workspace, workspace_bytes, batch,
                                        vsrc, rows, seq, cin, cout, stream);
   }
-  const long Ms = (long)batch * vsrc;
-  const int gx = fused_small_gx(Ms);
-  const int n_el = cout * kSeq * cin + cout;
-#define BOS(CIN_, CO_)                                                                           \
-  if (cin == CIN_ && cout == CO_) {                                                              \
-    hipLaunchKernelGGL((conv_bwd_out_mfma<CIN_, CO_>), dim3(gx), dim3(256), 0, st, dpre,         \
-                       inv_ptr, inv_row, (const int4*)inv_head, w, elu_y, x, dx, workspace, vsrc, \
-                       rows, Ms, batch, 0, 0);                                                   \
-    rc = launch_status("spiral_conv_bwd_small");                                                 \
-    if (rc || !dw) return rc;                                                                    \
-    hipLaunchKernelGGL(slab_reduce, dim3((unsigned)((n_el + 63) / 64)), dim3(1024), 0, st,        \
-                       workspace, gx, n_el, dw, cout * kSeq * cin, db);                          \
-    return launch_status("spiral_conv_bwd_small_reduce");                                        \
-  }
-  BOS(32, 1) BOS(32, 2) BOS(32, 3) BOS(64, 1) BOS(64, 2) BOS(64, 3)
-#undef BOS
+  rc = bwd_fused_small(x, CFSD_DT_F32, dpre, 0, inv_ptr, inv_row, inv_head, w, elu_y, dx, dw, db, workspace,
+                       batch, vsrc, rows, cin, cout, st);
+  if (rc != kNoShape) return rc;
   return set_error(CFSD_EINVAL, "spiral_conv_bwd: unsupported channels %d -> %d", cin, cout);
 }
 
@@ -2842,10 +2983,89 @@ extern "C" size_t cfsd_spiral_conv_bwd_rowsub_workspace(int batch, int vsrc, int
          sizeof(float);
 }
 
+// The dG tiles of a row-subset layer, with its few-row dW slabs in the same
+// launch when d.nb > 0 (d zeroed: dG only).
+static int launch_rowsub_pair(const DgArgs& a, const DwLatArgs& d, int cin, int cout, hipStream_t st) {
+  return for_shape(RowsubShapes{}, cin, cout, [&](auto s) {
+    using S = decltype(s);
+    hipLaunchKernelGGL((conv_bwd_rowsub_pair<S::cin, S::cout>), dim3((unsigned)(a.nb + d.nb)), dim3(256),
+                       (dg_lds_floats<S::cin, S::cout>(a.n_groups) * sizeof(float)), st, a, d);
+    return launch_status("spiral_conv_bwd_rowsub_pair");
+  });
+}
+
+// dx gathered from dG (dg_el floats) through the flat inverse list; elu_y and
+// dx stored as dx_dt, in the layout dxvm.  32 input channels (RowsubShapes).
+static int rowsub_gather(const float* dg, size_t dg_el, const int32_t* inv_flat, int flat_width, const void* elu_y,
+                         void* dx, int dx_dt, int dxvm, int batch, int vsrc, int rows, hipStream_t st) {
+  const long threads = (long)batch * vsrc * (32 / 4);
+  const dim3 gg((unsigned)((threads + 255) / 256));
+  return for_value(GatherGroups{}, flat_width / 4, [&](auto g) {
+    return for_storage(dx_dt, [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL((conv_dx_rowsub_gather<32, decltype(g)::value, T>), gg, dim3(256), 0, st, dg,
+                         (const int4*)inv_flat, (const T*)elu_y, (T*)dx, vsrc, rows, batch * vsrc,
+                         (int)(dg_el * sizeof(float)), batch, dxvm);
+      return launch_status("spiral_conv_bwd_rowsub_gather");
+    });
+  });
+}
+
 static int bwd_rowsub(const float* x, int xvm, const int32_t* idx, const float* dpre, const int32_t* inv_flat,
                       int flat_width, const float* w, const float* elu_y, float* dx, float* dw, float* db,
                       float* workspace, size_t workspace_bytes, int batch, int vsrc, int rows, int seq, int cin,
-                      int cout, void* stream);
+                      int cout, void* stream) {
+  int rc = check_conv_args(x, idx, dpre, batch, vsrc, rows, seq, cin, cout);
+  if (rc) return rc;
+  if (!inv_flat || !w || !dx || !workspace)
+    return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub: null inv_flat / w / dx / workspace");
+  if (!rowsub_shape(cin, cout))
+    return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub: unsupported channels %d -> %d", cin, cout);
+  if ((rc = check_flat_width("spiral_conv_bwd_rowsub", flat_width))) return rc;
+  if ((rc = check_inv_aligned(inv_flat, "inv_flat"))) return rc;
+  if ((rc = check_dw_db(dw, db))) return rc;
+  if ((rc = check_workspace(workspace_bytes,
+                            cfsd_spiral_conv_bwd_rowsub_workspace(batch, vsrc, rows, seq, cin, cout))))
+    return rc;
+  const size_t dg_el = (size_t)batch * rows * kSeq * cin;
+  if (dg_el * sizeof(float) >= (size_t)kAbsentRow)
+    return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub: dG of %zu floats exceeds 32-bit buffer offsets", dg_el);
+  hipStream_t st = (hipStream_t)stream;
+  const DwGeom g = dw_geom(batch, rows, cin, cout);
+  float* dg = workspace + rowsub_slab_floats(batch, rows, cin, cout);
+  const int total = batch * rows;
+  const int n_tiles = kSeq * cin / 16;
+  DgArgs a{dpre, w, dg, total, 0, 0};
+  a.n_groups = rowsub_groups((total + 15) / 16, n_tiles);
+  a.nb = (int)(((total + 15) / 16 + 3) / 4) * a.n_groups;
+  const bool lat = g.kind == kDwLat;
+  float* ws_db = workspace + (size_t)g.gx * dw_units(cin, cout) * 1024;
+  DwLatArgs d{x, idx, dpre, workspace, ws_db, vsrc, rows, total, g.rchunk, g.gx, 0, batch, xvm, 0};
+  if (lat) d.nb = (int)((lat_tasks(g.gx, dw_units(cin, cout)) + 3) / 4);
+  if (xvm && !lat) return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub_x: vertex-major x needs a few-row layer");
+  if (lat && batch % 16 == 0 && cin == 32 && cout == 32 && (flat_width == 8 || flat_width == 12 || flat_width == 16)) {
+    // 16-mesh batches, 32 -> 32: dx straight from dpre by the flat-list MFMA
+    // kernel (one 16-mesh MFMA tile per list entry; dx in x's layout) paired
+    // with the dW slabs in one launch -- no dG round trip, no gather launch
+    // (the fp32 step's E1: 22.1 + 8.2 -> 22.0 us, E2: 8.5 + 5.1 -> 11.9 us;
+    // E3, 32 -> 64 on 267 vertices: 14.9 vs 7.0 + 4.8 us, keeps the dG path).
+    // dx sums each entry's MFMA products into one accumulator (the dG path
+    // rounds every dG element first): equal to fp32 rounding, not bit for bit.
+    rc = vm32::launch_bwd_flat_pair(dpre, inv_flat, flat_width, w, elu_y, dx, xvm, vsrc, rows, batch, cin, cout,
+                                    d, lat_tasks(g.gx, dw_units(cin, cout)), st);
+    if (rc) return rc;
+    return reduce_dw_units(!dw, cin, cout, workspace, ws_db, dw, db, lat_slabs(g.gx), st);
+  }
+  if ((rc = launch_rowsub_pair(a, d, cin, cout, st))) return rc;
+  if (lat) {
+    rc = reduce_dw_units(!dw, cin, cout, workspace, ws_db, dw, db, lat_slabs(g.gx), st);
+  } else {  // many rows: the persistent dW kernel, same slab layout
+    rc = cfsd_spiral_conv_bwd_weight(x, idx, dpre, dw, db, workspace, workspace_bytes, batch, vsrc,
+                                     rows, seq, cin, cout, stream);
+  }
+  if (rc) return rc;
+  return rowsub_gather(dg, dg_el, inv_flat, flat_width, elu_y, dx, CFSD_DT_F32, xvm, batch, vsrc, rows, st);
+}
 
 extern "C" int cfsd_spiral_conv_bwd_rowsub(const float* x, const int32_t* idx, const float* dpre,
                                            const int32_t* inv_flat, int flat_width,
@@ -2864,94 +3084,8 @@ extern "C" int cfsd_spiral_conv_bwd_rowsub_x(const float* x, int x_dt, const int
                                              int cout, void* stream) {
   if (CFSD_DT_TYPE(x_dt) != CFSD_DT_F32 || (x_dt & ~(CFSD_VM | 0xf)))
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub_x: x must be fp32 (either layout)");
-  return bwd_rowsub(x, (x_dt & CFSD_VM) != 0, idx, dpre, inv_flat, flat_width, w, elu_y, dx, dw, db, workspace,
+  return bwd_rowsub(x, vm_of(x_dt), idx, dpre, inv_flat, flat_width, w, elu_y, dx, dw, db, workspace,
                     workspace_bytes, batch, vsrc, rows, seq, cin, cout, stream);
-}
-
-static int bwd_rowsub(const float* x, int xvm, const int32_t* idx, const float* dpre, const int32_t* inv_flat,
-                      int flat_width, const float* w, const float* elu_y, float* dx, float* dw, float* db,
-                      float* workspace, size_t workspace_bytes, int batch, int vsrc, int rows, int seq, int cin,
-                      int cout, void* stream) {
-  int rc = check_conv_args(x, idx, dpre, batch, vsrc, rows, seq, cin, cout);
-  if (rc) return rc;
-  if (!inv_flat || !w || !dx || !workspace)
-    return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub: null inv_flat / w / dx / workspace");
-  if (!rowsub_shape(cin, cout))
-    return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub: unsupported channels %d -> %d", cin, cout);
-  if (flat_width <= 0 || flat_width > 16 || flat_width % 4)
-    return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub: flat_width %d not in {4, 8, 12, 16}", flat_width);
-  if ((uintptr_t)inv_flat & 15) return set_error(CFSD_EINVAL, "inv_flat must be 16-B aligned");
-  if ((dw == nullptr) != (db == nullptr))
-    return set_error(CFSD_EINVAL, "dw and db must both be set (or both NULL: deferred)");
-  const size_t need = cfsd_spiral_conv_bwd_rowsub_workspace(batch, vsrc, rows, seq, cin, cout);
-  if (workspace_bytes < need)
-    return set_error(CFSD_EWORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
-  const size_t dg_el = (size_t)batch * rows * kSeq * cin;
-  if (dg_el * sizeof(float) >= (size_t)kAbsentRow)
-    return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub: dG of %zu floats exceeds 32-bit buffer offsets", dg_el);
-  hipStream_t st = (hipStream_t)stream;
-  const DwGeom g = dw_geom(batch, rows, cin, cout);
-  float* dg = workspace + rowsub_slab_floats(batch, rows, cin, cout);
-  const int total = batch * rows;
-  const int n_tiles = kSeq * cin / 16;
-  DgArgs a{dpre, w, dg, total, 0, 0};
-  a.n_groups = rowsub_groups((total + 15) / 16, n_tiles);
-  a.nb = (int)(((total + 15) / 16 + 3) / 4) * a.n_groups;
-  const bool lat = g.kind == kDwLat;
-  float* ws_db = workspace + (size_t)g.gx * dw_units(cin, cout) * 1024;
-  DwLatArgs d{x, idx, dpre, workspace, ws_db, vsrc, rows, total, g.rchunk, g.gx, 0, batch, xvm, 0};
-  if (lat) d.nb = (int)((lat_tasks(g.gx, dw_units(cin, cout)) + 3) / 4);
-  if (xvm && !lat) return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub_x: vertex-major x needs a few-row layer");
-  const int n_el = cout * kSeq * cin + cout;
-  if (lat && batch % 16 == 0 && cin == 32 && cout == 32 && (flat_width == 8 || flat_width == 12 || flat_width == 16)) {
-    // 16-mesh batches, 32 -> 32: dx straight from dpre by the flat-list MFMA
-    // kernel (one 16-mesh MFMA tile per list entry; dx in x's layout) paired
-    // with the dW slabs in one launch -- no dG round trip, no gather launch
-    // (the fp32 step's E1: 22.1 + 8.2 -> 22.0 us, E2: 8.5 + 5.1 -> 11.9 us;
-    // E3, 32 -> 64 on 267 vertices: 14.9 vs 7.0 + 4.8 us, keeps the dG path).
-    // dx sums each entry's MFMA products into one accumulator (the dG path
-    // rounds every dG element first): equal to fp32 rounding, not bit for bit.
-    rc = vm32::launch_bwd_flat_pair(dpre, inv_flat, flat_width, w, elu_y, dx, xvm, vsrc, rows, batch, cin, cout,
-                                    d, lat_tasks(g.gx, dw_units(cin, cout)), st);
-    if (rc || !dw) return rc;
-#define RSR(CIN_, COUT_)                                                                          \
-    if (cin == CIN_ && cout == COUT_)                                                             \
-      hipLaunchKernelGGL((conv_dw_reduce<CIN_, COUT_>), dim3((unsigned)((n_el + 63) / 64)),       \
-                         dim3(1024), 0, st, workspace, ws_db, dw, db, lat_slabs(g.gx));
-    RSR(32, 32) RSR(32, 64)
-#undef RSR
-    return launch_status("spiral_conv_bwd_rowsub_reduce");
-  }
-  const dim3 grid((unsigned)(a.nb + d.nb));
-#define RSP(CIN_, COUT_)                                                                          \
-  if (cin == CIN_ && cout == COUT_) {                                                             \
-    hipLaunchKernelGGL((conv_bwd_rowsub_pair<CIN_, COUT_>), grid, dim3(256),                      \
-                       (dg_lds_floats<CIN_, COUT_>(a.n_groups) * sizeof(float)), st, a, d);                  \
-    rc = launch_status("spiral_conv_bwd_rowsub_pair");                                           \
-    if (!rc && lat && dw)                                                                         \
-      hipLaunchKernelGGL((conv_dw_reduce<CIN_, COUT_>), dim3((unsigned)((n_el + 63) / 64)),       \
-                         dim3(1024), 0, st, workspace, ws_db, dw, db, lat_slabs(g.gx));           \
-  }
-  RSP(32, 32) RSP(32, 64)
-#undef RSP
-  if (rc || (rc = launch_status("spiral_conv_bwd_rowsub_reduce"))) return rc;
-  if (!lat) {  // many rows: the persistent dW kernel, same slab layout
-    rc = cfsd_spiral_conv_bwd_weight(x, idx, dpre, dw, db, workspace, workspace_bytes, batch, vsrc,
-                                     rows, seq, cin, cout, stream);
-    if (rc) return rc;
-  }
-  const long threads = (long)batch * vsrc * (cin / 4);
-  const dim3 gg((unsigned)((threads + 255) / 256));
-  const int G = flat_width / 4, M = batch * vsrc;
-#define RSG(CIN_, G_)                                                                             \
-  if (cin == CIN_ && G == G_) {                                                                   \
-    hipLaunchKernelGGL((conv_dx_rowsub_gather<CIN_, G_>), gg, dim3(256), 0, st, dg,               \
-                       (const int4*)inv_flat, elu_y, dx, vsrc, rows, M, (int)(dg_el * sizeof(float)), batch, xvm); \
-    return launch_status("spiral_conv_bwd_rowsub_gather");                                       \
-  }
-  RSG(32, 1) RSG(32, 2) RSG(32, 3) RSG(32, 4)
-#undef RSG
-  return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub: unsupported channels %d -> %d", cin, cout);
 }
 
 extern "C" size_t cfsd_spiral_conv_bwd_data_rowsub_workspace(int batch, int rows, int seq, int cin) {
@@ -2969,20 +3103,17 @@ extern "C" int cfsd_spiral_conv_bwd_data_rowsub(const float* dpre, const int32_t
   if (!dx || !workspace) return set_error(CFSD_EINVAL, "spiral_conv_bwd_data_rowsub: null dx / workspace");
   if (!rowsub_shape(cin, cout))
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_data_rowsub: unsupported channels %d -> %d", cin, cout);
-  const int dxvm = (dx_dt & CFSD_VM) != 0;  // dx and elu_y vertex-major
+  const int dxvm = vm_of(dx_dt);  // dx and elu_y vertex-major
   dx_dt = CFSD_DT_TYPE(dx_dt);
   if (dx_dt != CFSD_DT_F32 && dx_dt != CFSD_DT_BF16) return set_error(CFSD_EINVAL, "bad dx dtype %d", dx_dt);
-  if (flat_width <= 0 || flat_width > 16 || flat_width % 4)
-    return set_error(CFSD_EINVAL, "spiral_conv_bwd_data_rowsub: flat_width %d not in {4, 8, 12, 16}", flat_width);
-  if ((uintptr_t)inv_flat & 15) return set_error(CFSD_EINVAL, "inv_flat must be 16-B aligned");
+  if ((rc = check_flat_width("spiral_conv_bwd_data_rowsub", flat_width))) return rc;
+  if ((rc = check_inv_aligned(inv_flat, "inv_flat"))) return rc;
   const size_t dg_el = (size_t)batch * rows * kSeq * cin;
-  if (workspace_bytes < rowsub_dg_floats(batch, rows, cin) * sizeof(float))
-    return set_error(CFSD_EWORKSPACE, "workspace %zu < %zu bytes", workspace_bytes,
-                     rowsub_dg_floats(batch, rows, cin) * sizeof(float));
+  if ((rc = check_workspace(workspace_bytes, rowsub_dg_floats(batch, rows, cin) * sizeof(float)))) return rc;
   if (dg_el * sizeof(float) >= (size_t)kAbsentRow)
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_data_rowsub: dG exceeds 32-bit buffer offsets");
   hipStream_t st = (hipStream_t)stream;
-  if (batch % 16 == 0 && cout == 32 && (flat_width == 4 || flat_width == 8 || flat_width == 12 || flat_width == 16)) {
+  if (batch % 16 == 0 && cout == 32) {
     // 16-mesh batches, 32 -> 32: dx straight from dpre by the flat-list MFMA
     // kernel (no dG round trip, no gather launch; the bf16 step's E1: dG 11.0
     // + gather 7.0 us), the fp32 sum rounded once for bf16 storage
@@ -2995,30 +3126,8 @@ extern "C" int cfsd_spiral_conv_bwd_data_rowsub(const float* dpre, const int32_t
   const int total = batch * rows;
   DgArgs a{dpre, w, workspace, total, rowsub_groups((total + 15) / 16, kSeq * cin / 16), 0};
   a.nb = (int)(((total + 15) / 16 + 3) / 4) * a.n_groups;
-  DwLatArgs d{};  // no dW half
-  if (cout == 32)
-    hipLaunchKernelGGL((conv_bwd_rowsub_pair<32, 32>), dim3(a.nb), dim3(256),
-                       (dg_lds_floats<32, 32>(a.n_groups) * sizeof(float)), st, a, d);
-  else
-    hipLaunchKernelGGL((conv_bwd_rowsub_pair<32, 64>), dim3(a.nb), dim3(256),
-                       (dg_lds_floats<32, 64>(a.n_groups) * sizeof(float)), st, a, d);
-  if ((rc = launch_status("spiral_conv_bwd_data_rowsub_dg"))) return rc;
-  const long threads = (long)batch * vsrc * (cin / 4);
-  const dim3 gg((unsigned)((threads + 255) / 256));
-  const int G = flat_width / 4, M = batch * vsrc, dgb = (int)(dg_el * sizeof(float));
-#define RSG2(G_)                                                                                   \
-  if (G == G_) {                                                                                   \
-    if (dx_dt == CFSD_DT_BF16)                                                                     \
-      hipLaunchKernelGGL((conv_dx_rowsub_gather<32, G_, bf16_t>), gg, dim3(256), 0, st, workspace, \
-                         (const int4*)inv_flat, (const bf16_t*)elu_y, (bf16_t*)dx, vsrc, rows, M, dgb, batch, dxvm); \
-    else                                                                                           \
-      hipLaunchKernelGGL((conv_dx_rowsub_gather<32, G_, float>), gg, dim3(256), 0, st, workspace,  \
-                         (const int4*)inv_flat, (const float*)elu_y, (float*)dx, vsrc, rows, M, dgb, batch, dxvm); \
-    return launch_status("spiral_conv_bwd_data_rowsub_gather");                                   \
-  }
-  RSG2(1) RSG2(2) RSG2(3) RSG2(4)
-#undef RSG2
-  return set_error(CFSD_EINVAL, "spiral_conv_bwd_data_rowsub: bad flat_width");
+  if ((rc = launch_rowsub_pair(a, DwLatArgs{}, cin, cout, st))) return rc;  // no dW half
+  return rowsub_gather(workspace, dg_el, inv_flat, flat_width, elu_y, dx, dx_dt, dxvm, batch, vsrc, rows, st);
 }
 
 extern "C" int cfsd_spiral_gather(const float* x, const int32_t* idx, float* g, int batch,
@@ -3049,14 +3158,6 @@ extern "C" int cfsd_spiral_gather(const float* x, const int32_t* idx, float* g, 
 // (spiral_conv_bf16.hip) and the xyz layers to the small-channel kernels
 // above, instantiated for bf16 operands.  Weights: `w` fp32 master (small
 // layers), `w_bf16` its bf16 shadow (MFMA layers).
-static bool mfma_shape(int cin, int cout) {
-  return (cin == 32 || cin == 64) && (cout == 32 || cout == 64);
-}
-static bool dt_ok(int dt) {
-  return (dt & ~(CFSD_VM | 0xf)) == 0 && (CFSD_DT_TYPE(dt) == CFSD_DT_F32 || CFSD_DT_TYPE(dt) == CFSD_DT_BF16);
-}
-static int vm_of(int dt) { return (dt & CFSD_VM) != 0; }
-
 extern "C" int cfsd_spiral_conv_fwd_in_swap(const float* data, const int32_t* batch_idx,
                                             const uint8_t* region_mask, const int32_t* key, int bs, int n_meshes,
                                             int n_regions, float* x, int x_dt, const int32_t* idx, const float* w,
@@ -3068,7 +3169,8 @@ extern "C" int cfsd_spiral_conv_fwd_in_swap(const float* data, const int32_t* ba
     return set_error(CFSD_EINVAL, "spiral_conv_fwd_in_swap: bad sizes");
   if (cin != 3 || (cout != 32 && cout != 64))
     return set_error(CFSD_EINVAL, "spiral_conv_fwd_in_swap: the xyz input conv (3 -> 32/64) only");
-  if (act != CFSD_ACT_NONE && act != CFSD_ACT_ELU) return set_error(CFSD_EINVAL, "bad act %d", act);
+  int rc = check_act(act);
+  if (rc) return rc;
   if (!dt_ok(x_dt) || !dt_ok(y_dt) || CFSD_DT_TYPE(x_dt) != CFSD_DT_F32)
     return set_error(CFSD_EINVAL, "spiral_conv_fwd_in_swap: fp32 x, fp32 or bf16 y");
   const int batch = bs * bs;
@@ -3080,25 +3182,26 @@ extern "C" int cfsd_spiral_conv_fwd_in_swap(const float* data, const int32_t* ba
   const int n_conv = (int)((tiles + 3) / 4 < 2048 ? (tiles + 3) / 4 : 2048);
   const dim3 grid((unsigned)(n_conv + (swap_total + 255) / 256));
   const hipStream_t st = (hipStream_t)stream;
-  const bool ybf = CFSD_DT_TYPE(y_dt) == CFSD_DT_BF16;
-#define FSW(CO_, ACT_, TY_)                                                                                 \
-  hipLaunchKernelGGL((conv_fwd_in_swap<3, CO_, ACT_, TY_>), grid, dim3(256), 0, st, sw, x, n_conv, swap_total, \
-                     idx, w, bias, (TY_*)y, vsrc, rows, M, batch, xvm, yvm)
-  if (cout == 32) {
-    if (act == CFSD_ACT_ELU) {
-      if (ybf) FSW(32, CFSD_ACT_ELU, bf16_t); else FSW(32, CFSD_ACT_ELU, float);
-    } else {
-      if (ybf) FSW(32, CFSD_ACT_NONE, bf16_t); else FSW(32, CFSD_ACT_NONE, float);
-    }
-  } else {
-    if (act == CFSD_ACT_ELU) {
-      if (ybf) FSW(64, CFSD_ACT_ELU, bf16_t); else FSW(64, CFSD_ACT_ELU, float);
-    } else {
-      if (ybf) FSW(64, CFSD_ACT_NONE, bf16_t); else FSW(64, CFSD_ACT_NONE, float);
-    }
-  }
-#undef FSW
-  return launch_status("spiral_conv_fwd_in_swap");
+  return for_value(SwapCouts{}, cout, [&](auto co) {
+    return for_value(Acts{}, act, [&](auto a) {
+      return for_storage(y_dt, [&](auto t) {
+        using TY = typename decltype(t)::type;
+        hipLaunchKernelGGL((conv_fwd_in_swap<3, decltype(co)::value, decltype(a)::value, TY>), grid, dim3(256), 0, st,
+                           sw, x, n_conv, swap_total, idx, w, bias, (TY*)y, vsrc, rows, M, batch, xvm, yvm);
+        return launch_status("spiral_conv_fwd_in_swap");
+      });
+    });
+  });
+}
+
+// fp32 vertex-major 32 -> 32 with few rows (an Enblock's kept rows): 16x16 tasks
+template <int ACT>
+static int launch_fwd_lat_x(const float* x, int xvm, const int* idx, const float* w, const float* bias, float* y,
+                            int yvm, int vsrc, int rows, int batch, hipStream_t st) {
+  const long M = (long)batch * rows, tasks = (M + 15) / 16 * 2;
+  hipLaunchKernelGGL((conv_fwd_lat<32, 32, ACT, 1>), dim3((unsigned)((tasks + 3) / 4)), dim3(256), 0, st, x, idx, w,
+                     bias, y, vsrc, rows, M, batch, xvm, yvm);
+  return launch_status("spiral_conv_fwd_lat_x");
 }
 
 extern "C" int cfsd_spiral_conv_fwd_x(const void* x, int x_dt, const int32_t* idx, const float* w,
@@ -3107,8 +3210,8 @@ extern "C" int cfsd_spiral_conv_fwd_x(const void* x, int x_dt, const int32_t* id
                                       int act, void* stream) {
   int rc = check_conv_args(x, idx, y, batch, vsrc, rows, seq, cin, cout);
   if (rc) return rc;
-  if (!dt_ok(x_dt) || !dt_ok(y_dt)) return set_error(CFSD_EINVAL, "spiral_conv_fwd_x: bad dtype");
-  if (act != CFSD_ACT_NONE && act != CFSD_ACT_ELU) return set_error(CFSD_EINVAL, "bad act %d", act);
+  if ((rc = check_dt("spiral_conv_fwd_x", x_dt)) || (rc = check_dt("spiral_conv_fwd_x", y_dt))) return rc;
+  if ((rc = check_act(act))) return rc;
   const hipStream_t st = (hipStream_t)stream;
   const long M = (long)batch * rows;
   const int xvm = vm_of(x_dt), yvm = vm_of(y_dt);
@@ -3124,90 +3227,24 @@ extern "C" int cfsd_spiral_conv_fwd_x(const void* x, int x_dt, const int32_t* id
     if (y_dt != CFSD_DT_F32) return set_error(CFSD_EINVAL, "spiral_conv_fwd_x: fp32 x needs fp32 y");
     if (coarse::fwd_ks_enabled(M, cin, cout))
       return fwd_coarse((const float*)x, xvm, idx, w, bias, (float*)y, yvm, vsrc, rows, batch, cin, cout, act, st);
-    if (M < kLatFwdMax && cin == 32 && cout == 32) {  // few rows (an Enblock's kept rows): 16x16 tasks
-      const long tasks = (M + 15) / 16 * 2;
-      if (act == CFSD_ACT_ELU)
-        hipLaunchKernelGGL((conv_fwd_lat<32, 32, CFSD_ACT_ELU, 1>), dim3((unsigned)((tasks + 3) / 4)), dim3(256),
-                           0, st, (const float*)x, idx, w, bias, (float*)y, vsrc, rows, M, batch, xvm, yvm);
-      else
-        hipLaunchKernelGGL((conv_fwd_lat<32, 32, CFSD_ACT_NONE, 1>), dim3((unsigned)((tasks + 3) / 4)), dim3(256),
-                           0, st, (const float*)x, idx, w, bias, (float*)y, vsrc, rows, M, batch, xvm, yvm);
-      return launch_status("spiral_conv_fwd_lat_x");
-    }
+    if (M < kLatFwdMax && cin == 32 && cout == 32)
+      return for_value(Acts{}, act, [&](auto a) {
+        return launch_fwd_lat_x<decltype(a)::value>((const float*)x, xvm, idx, w, bias, (float*)y, yvm, vsrc, rows,
+                                                    batch, st);
+      });
     return vm32::launch_fwd((const float*)x, idx, w, bias, (float*)y, yvm, vsrc, rows, batch, cin, cout, act, st);
   }
-  if (cin <= 3 && (cout == 32 || cout == 64) && x_dt == CFSD_DT_F32 && y_dt == CFSD_DT_F32) {
-#define FINF(CS_, CO_)                                                                           \
-  if (cin == CS_ && cout == CO_) {                                                               \
-    if (act == CFSD_ACT_ELU)                                                                     \
-      hipLaunchKernelGGL((conv_fwd_in_mfma<CS_, CO_, CFSD_ACT_ELU, float>), dim3(gp), dim3(256),  \
-                         0, st, (const float*)x, idx, w, bias, (float*)y, vsrc, rows, M, batch,  \
-                         xvm, yvm);                                                              \
-    else                                                                                         \
-      hipLaunchKernelGGL((conv_fwd_in_mfma<CS_, CO_, CFSD_ACT_NONE, float>), dim3(gp), dim3(256), \
-                         0, st, (const float*)x, idx, w, bias, (float*)y, vsrc, rows, M, batch,  \
-                         xvm, yvm);                                                              \
-    return launch_status("spiral_conv_fwd_in_x");                                                \
-  }
-    const long tiles = (M + 31) / 32;
-    const unsigned gp = (unsigned)((tiles + 3) / 4 < 2048 ? (tiles + 3) / 4 : 2048);
-    FINF(1, 32) FINF(2, 32) FINF(3, 32) FINF(1, 64) FINF(2, 64) FINF(3, 64)
-#undef FINF
+  // (fp32 batch-major MFMA shapes are cfsd_spiral_conv_fwd's: none of the routes below takes them)
+  if (x_dt == CFSD_DT_F32) {  // the xyz input conv, fp32 or bf16 y
+    rc = fwd_xyz_in((const float*)x, xvm, idx, w, bias, y, y_dt, yvm, vsrc, rows, batch, cin, cout, act, st);
+    if (rc != kNoShape) return rc;
   }
   if (cout <= 3 && cin == 32 && xvm && batch % 8 == 0 && y_dt == CFSD_DT_F32)  // xyz output conv, vertex-major x
     return vm32::launch_fwd_out(x, x_dt == CFSD_DT_BF16, idx, w, bias, (float*)y, yvm, vsrc, rows, batch, cout, act,
                                 st);
-  if (cout <= 3 && (cin == 16 || cin == 32 || cin == 64) && x_dt == CFSD_DT_F32 && y_dt == CFSD_DT_F32) {
-#define FOUTF(CI_, CO_)                                                                           \
-  if (cin == CI_ && cout == CO_) {                                                                \
-    if (act == CFSD_ACT_ELU) {                                                                    \
-      auto k = conv_fwd_out_small<CI_, CO_, CFSD_ACT_ELU, float>;                                 \
-      hipLaunchKernelGGL(k, dim3(small_grid(k, M)), dim3(256), 0, st, (const float*)x, idx, w,    \
-                         bias, (float*)y, vsrc, rows, M, batch, xvm, yvm);                        \
-    } else {                                                                                      \
-      auto k = conv_fwd_out_small<CI_, CO_, CFSD_ACT_NONE, float>;                                \
-      hipLaunchKernelGGL(k, dim3(small_grid(k, M)), dim3(256), 0, st, (const float*)x, idx, w,    \
-                         bias, (float*)y, vsrc, rows, M, batch, xvm, yvm);                        \
-    }                                                                                             \
-    return launch_status("spiral_conv_fwd_out_x");                                                \
-  }
-    FOUTF(16, 3) FOUTF(32, 3) FOUTF(64, 3) FOUTF(32, 1) FOUTF(32, 2)
-#undef FOUTF
-  }
-  if (cin <= 3 && (cout == 32 || cout == 64) && x_dt == CFSD_DT_F32 && y_dt == CFSD_DT_BF16) {
-    const long tiles = (M + 31) / 32;
-    const unsigned gp = (unsigned)((tiles + 3) / 4 < 2048 ? (tiles + 3) / 4 : 2048);
-#define FINB(CS_, CO_)                                                                           \
-  if (cin == CS_ && cout == CO_) {                                                               \
-    if (act == CFSD_ACT_ELU)                                                                     \
-      hipLaunchKernelGGL((conv_fwd_in_mfma<CS_, CO_, CFSD_ACT_ELU, bf16_t>), dim3(gp), dim3(256), \
-                         0, st, (const float*)x, idx, w, bias, (bf16_t*)y, vsrc, rows, M, batch, \
-                         xvm, yvm);                                                              \
-    else                                                                                         \
-      hipLaunchKernelGGL((conv_fwd_in_mfma<CS_, CO_, CFSD_ACT_NONE, bf16_t>), dim3(gp), dim3(256), \
-                         0, st, (const float*)x, idx, w, bias, (bf16_t*)y, vsrc, rows, M, batch, \
-                         xvm, yvm);                                                              \
-    return launch_status("spiral_conv_fwd_in_bf16");                                             \
-  }
-    FINB(1, 32) FINB(2, 32) FINB(3, 32) FINB(1, 64) FINB(2, 64) FINB(3, 64)
-#undef FINB
-  }
-  if (cout <= 3 && (cin == 16 || cin == 32 || cin == 64) && x_dt == CFSD_DT_BF16 && y_dt == CFSD_DT_F32) {
-#define FOUTB(CI_, CO_)                                                                           \
-  if (cin == CI_ && cout == CO_) {                                                                \
-    if (act == CFSD_ACT_ELU) {                                                                    \
-      auto k = conv_fwd_out_small<CI_, CO_, CFSD_ACT_ELU, bf16_t>;                                \
-      hipLaunchKernelGGL(k, dim3(small_grid(k, M)), dim3(256), 0, st, (const bf16_t*)x, idx, w,   \
-                         bias, (float*)y, vsrc, rows, M, batch, xvm, yvm);                        \
-    } else {                                                                                      \
-      auto k = conv_fwd_out_small<CI_, CO_, CFSD_ACT_NONE, bf16_t>;                               \
-      hipLaunchKernelGGL(k, dim3(small_grid(k, M)), dim3(256), 0, st, (const bf16_t*)x, idx, w,   \
-                         bias, (float*)y, vsrc, rows, M, batch, xvm, yvm);                        \
-    }                                                                                             \
-    return launch_status("spiral_conv_fwd_out_bf16");                                             \
-  }
-    FOUTB(16, 3) FOUTB(32, 3) FOUTB(64, 3) FOUTB(32, 1) FOUTB(32, 2)
-#undef FOUTB
+  if (y_dt == CFSD_DT_F32) {  // a small-output conv, fp32 or bf16 x
+    rc = fwd_out_small(x, x_dt, xvm, idx, w, bias, (float*)y, yvm, vsrc, rows, batch, cin, cout, act, st);
+    if (rc != kNoShape) return rc;
   }
   return set_error(CFSD_EINVAL, "spiral_conv_fwd_x: unsupported %d -> %d with dtypes %d -> %d", cin, cout,
                    x_dt, y_dt);
@@ -3221,11 +3258,11 @@ extern "C" int cfsd_spiral_conv_bwd_data_x(const void* dpre, int dpre_dt, const 
   int rc = check_conv_args(dpre, inv_ptr, inv_row, batch, vsrc, rows, seq, cin, cout);
   if (rc) return rc;
   if (!w_bf16 || !dx || !inv_head) return set_error(CFSD_EINVAL, "null w_bf16/dx/inv_head");
-  if (!dt_ok(dpre_dt) || !dt_ok(dx_dt) || CFSD_DT_TYPE(dx_dt) != CFSD_DT_BF16)
-    return set_error(CFSD_EINVAL, "spiral_conv_bwd_data_x: bad dtype");
-  if ((uintptr_t)inv_head & 15) return set_error(CFSD_EINVAL, "inv_head must be 16-B aligned");
-  if ((long)batch * rows * cout * (CFSD_DT_TYPE(dpre_dt) == CFSD_DT_F32 ? 4L : 2L) >= (1L << 31))
-    return set_error(CFSD_EINVAL, "dpre larger than 2 GiB (32-bit buffer offsets)");
+  if ((rc = check_dt("spiral_conv_bwd_data_x", dpre_dt)) || (rc = check_dt("spiral_conv_bwd_data_x", dx_dt)))
+    return rc;
+  if (CFSD_DT_TYPE(dx_dt) != CFSD_DT_BF16) return set_error(CFSD_EINVAL, "spiral_conv_bwd_data_x: dx must be bf16");
+  if ((rc = check_inv_aligned(inv_head, "inv_head"))) return rc;
+  if ((rc = check_dpre_bound(batch, rows, cout, dpre_dt))) return rc;
   if (!mfma_shape(cin, cout))
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_data_x: unsupported channels %d -> %d", cin, cout);
   return bf::launch_dx(dpre, dpre_dt, inv_ptr, inv_row, inv_head, (const bf16_t*)w_bf16,
@@ -3240,20 +3277,21 @@ extern "C" int cfsd_spiral_conv_bwd_data_flat(const void* dpre, int dpre_dt, con
   int rc = check_conv_args(dpre, inv_flat, w, batch, vsrc, rows, seq, cin, cout);
   if (rc) return rc;
   if (!dx) return set_error(CFSD_EINVAL, "spiral_conv_bwd_data_flat: null dx");
-  if (!dt_ok(dpre_dt) || !dt_ok(dx_dt) || !vm_of(dpre_dt) || !vm_of(dx_dt))
+  if ((rc = check_dt("spiral_conv_bwd_data_flat", dpre_dt)) || (rc = check_dt("spiral_conv_bwd_data_flat", dx_dt)))
+    return rc;
+  if (!vm_of(dpre_dt) || !vm_of(dx_dt))
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_data_flat: dpre and dx must be vertex-major (CFSD_VM)");
   if (CFSD_DT_TYPE(dx_dt) == CFSD_DT_F32) {  // fp32 operands and weights (spiral_conv_vm32.hip)
     if (CFSD_DT_TYPE(dpre_dt) != CFSD_DT_F32)
       return set_error(CFSD_EINVAL, "spiral_conv_bwd_data_flat: fp32 dx needs fp32 dpre");
-    if ((uintptr_t)inv_flat & 15) return set_error(CFSD_EINVAL, "inv_flat must be 16-B aligned");
+    if ((rc = check_inv_aligned(inv_flat, "inv_flat"))) return rc;
     return vm32::launch_dx_flat((const float*)dpre, 1, 1, inv_flat, flat_width, (const float*)w, (const float*)elu_y,
                                 (float*)dx, vsrc, rows, batch, cin, cout, (hipStream_t)stream);
   }
   if (!bf::vm16_ok(batch, cin, cout))
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_data_flat: batch %% 16 == 0 and 32 -> 32/64 channels only");
-  if ((uintptr_t)inv_flat & 15) return set_error(CFSD_EINVAL, "inv_flat must be 16-B aligned");
-  if ((long)batch * rows * cout * (CFSD_DT_TYPE(dpre_dt) == CFSD_DT_F32 ? 4L : 2L) >= (long)kAbsentRow)
-    return set_error(CFSD_EINVAL, "dpre exceeds 32-bit buffer offsets");
+  if ((rc = check_inv_aligned(inv_flat, "inv_flat"))) return rc;
+  if ((rc = check_dpre_bound(batch, rows, cout, dpre_dt, kAbsentRow))) return rc;
   return bf::launch_dx_flat_vm16(dpre, dpre_dt, inv_flat, flat_width, (const bf16_t*)w,
                                  (const bf16_t*)elu_y, (bf16_t*)dx, vsrc, rows, batch, cin, cout,
                                  (hipStream_t)stream);
@@ -3280,26 +3318,22 @@ extern "C" int cfsd_spiral_conv_bwd_flat_pair(const float* x, const int32_t* idx
   if (!vm_pair_shape(batch, rows, cin, cout))
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_flat_pair: 32 -> 32, batch %% 16 == 0, batch x rows >= %d only",
                      kLatDwMax);
-  if (flat_width <= 0 || flat_width > 20 || flat_width % 4)
-    return set_error(CFSD_EINVAL, "spiral_conv_bwd_flat_pair: flat_width %d not in {4, ..., 20}", flat_width);
-  if ((uintptr_t)inv_flat & 15) return set_error(CFSD_EINVAL, "inv_flat must be 16-B aligned");
-  if ((dw == nullptr) != (db == nullptr))
-    return set_error(CFSD_EINVAL, "dw and db must both be set (or both NULL: deferred)");
-  if ((long)batch * rows * cout * 4 >= (long)kAbsentRow || (long)batch * vsrc * cin * 4 >= (long)kAbsentRow)
-    return set_error(CFSD_EINVAL, "spiral_conv_bwd_flat_pair: operands exceed 32-bit buffer offsets");
-  const size_t need = cfsd_spiral_conv_bwd_flat_pair_workspace(batch, rows, seq, cin, cout);
-  if (workspace_bytes < need) return set_error(CFSD_EWORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  if ((rc = check_flat_width("spiral_conv_bwd_flat_pair", flat_width, 20))) return rc;
+  if ((rc = check_inv_aligned(inv_flat, "inv_flat"))) return rc;
+  if ((rc = check_dw_db(dw, db))) return rc;
+  if ((rc = check_dpre_bound(batch, rows, cout, CFSD_DT_F32, kAbsentRow))) return rc;
+  if ((long)batch * vsrc * cin * 4 >= (long)kAbsentRow)
+    return set_error(CFSD_EINVAL, "spiral_conv_bwd_flat_pair: x exceeds 32-bit buffer offsets");
+  if ((rc = check_workspace(workspace_bytes, cfsd_spiral_conv_bwd_flat_pair_workspace(batch, rows, seq, cin, cout))))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   const DwGeom g = dw_geom(batch, rows, cin, cout);
   float* ws_db = workspace + (size_t)g.gx * dw_units(cin, cout) * 1024;
   const int nslab = vm32::dw_slabs(batch, rows, g.gx);  // as cfsd_dw_reduce_batch's fused = 3 items
   rc = vm32::launch_bwd_vm_pair(dpre, inv_flat, flat_width, w, elu_y, dx, x, idx, workspace, ws_db, nslab, vsrc,
                                 rows, batch, st);
-  if (rc || !dw) return rc;
-  const int n_el = cout * kSeq * cin + cout;
-  hipLaunchKernelGGL((conv_dw_reduce<32, 32>), dim3((unsigned)((n_el + 63) / 64)), dim3(1024), 0, st, workspace,
-                     ws_db, dw, db, nslab);
-  return launch_status("spiral_conv_bwd_flat_pair_reduce");
+  if (rc) return rc;
+  return reduce_dw_units(!dw, cin, cout, workspace, ws_db, dw, db, nslab, st);
 }
 
 // ---- the bf16 step's Enblock pair (ABI 4.11): row-subset flat dx + vm16 dW slabs
@@ -3314,15 +3348,12 @@ extern "C" int cfsd_spiral_conv_bwd_rowsub_pair_bf16(const void* x, const int32_
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub_pair_bf16: null inv_flat / w / dx / workspace");
   if (cin != 32 || cout != 32 || batch % 16)
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub_pair_bf16: 32 -> 32, batch %% 16 == 0 only");
-  if (flat_width <= 0 || flat_width > 16 || flat_width % 4)
-    return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub_pair_bf16: flat_width %d not in {4, 8, 12, 16}",
-                     flat_width);
-  if ((uintptr_t)inv_flat & 15) return set_error(CFSD_EINVAL, "inv_flat must be 16-B aligned");
-  if ((long)batch * rows * cout * 4 >= (long)kAbsentRow)
-    return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub_pair_bf16: dpre exceeds 32-bit buffer offsets");
+  if ((rc = check_flat_width("spiral_conv_bwd_rowsub_pair_bf16", flat_width))) return rc;
+  if ((rc = check_inv_aligned(inv_flat, "inv_flat"))) return rc;
+  if ((rc = check_dpre_bound(batch, rows, cout, CFSD_DT_F32, kAbsentRow))) return rc;
   const int nslab = bf::dw_slabs(batch, rows, cin, cout);  // as cfsd_dw_reduce_batch's fused = 2 items
-  const size_t need = (size_t)nslab * ((size_t)cout * kSeq * cin + cout) * sizeof(float);
-  if (workspace_bytes < need) return set_error(CFSD_EWORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  if ((rc = check_workspace(workspace_bytes, (size_t)nslab * ((size_t)cout * kSeq * cin + cout) * sizeof(float))))
+    return rc;
   return bf::launch_bwd_rowsub16_pair((const bf16_t*)x, idx, dpre, inv_flat, flat_width, w, (const bf16_t*)elu_y,
                                       (bf16_t*)dx, workspace, nslab, vsrc, rows, batch, (hipStream_t)stream);
 }
@@ -3339,12 +3370,11 @@ extern "C" int cfsd_spiral_conv_bwd_flat_pair_bf16(const void* x, const int32_t*
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_flat_pair_bf16: null inv_flat / w / dx / workspace");
   if (cin != 32 || cout != 32 || batch % 16)
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_flat_pair_bf16: 32 -> 32, batch %% 16 == 0 only");
-  if (flat_width <= 0 || flat_width > 20 || flat_width % 4)
-    return set_error(CFSD_EINVAL, "spiral_conv_bwd_flat_pair_bf16: flat_width %d not in {4, ..., 20}", flat_width);
-  if ((uintptr_t)inv_flat & 15) return set_error(CFSD_EINVAL, "inv_flat must be 16-B aligned");
+  if ((rc = check_flat_width("spiral_conv_bwd_flat_pair_bf16", flat_width, 20))) return rc;
+  if ((rc = check_inv_aligned(inv_flat, "inv_flat"))) return rc;
   const int nslab = bf::dw_slabs(batch, rows, cin, cout);  // as cfsd_dw_reduce_batch's fused = 2 items
-  const size_t need = (size_t)nslab * ((size_t)cout * kSeq * cin + cout) * sizeof(float);
-  if (workspace_bytes < need) return set_error(CFSD_EWORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  if ((rc = check_workspace(workspace_bytes, (size_t)nslab * ((size_t)cout * kSeq * cin + cout) * sizeof(float))))
+    return rc;
   return bf::launch_bwd_vm16_pair((const bf16_t*)x, idx, (const bf16_t*)dpre, inv_flat, flat_width, (const bf16_t*)w,
                                   (const bf16_t*)elu_y, (bf16_t*)dx, workspace, nslab, vsrc, rows, batch,
                                   (hipStream_t)stream);
@@ -3365,17 +3395,13 @@ extern "C" int cfsd_spiral_conv_bwd_weight_x(const void* x, int x_dt, const int3
                                              void* stream) {
   int rc = check_conv_args(x, idx, dpre, batch, vsrc, rows, seq, cin, cout);
   if (rc) return rc;
-  if (!dt_ok(x_dt) || !dt_ok(dpre_dt)) return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight_x: bad dtype");
+  if ((rc = check_dt("spiral_conv_bwd_weight_x", x_dt)) || (rc = check_dt("spiral_conv_bwd_weight_x", dpre_dt)))
+    return rc;
   if (!workspace) return set_error(CFSD_EINVAL, "null workspace");
-  if ((dw == nullptr) != (db == nullptr))
-    return set_error(CFSD_EINVAL, "dw and db must both be set (or both NULL: deferred)");
-  const size_t need = cfsd_spiral_conv_bwd_weight_x_workspace(batch, rows, seq, cin, cout);
-  if (workspace_bytes < need)
-    return set_error(CFSD_EWORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  if ((rc = check_dw_db(dw, db))) return rc;
+  if ((rc = check_workspace(workspace_bytes, cfsd_spiral_conv_bwd_weight_x_workspace(batch, rows, seq, cin, cout))))
+    return rc;
   const hipStream_t st = (hipStream_t)stream;
-  const long M = (long)batch * rows;
-  const int n_el = cout * kSeq * cin + cout;
-  const dim3 rg((unsigned)((n_el + 63) / 64));
   const int xvm = vm_of(x_dt), dpvm = vm_of(dpre_dt);
   x_dt = CFSD_DT_TYPE(x_dt);
   int n_slabs = 0;
@@ -3386,34 +3412,20 @@ extern "C" int cfsd_spiral_conv_bwd_weight_x(const void* x, int x_dt, const int3
                   vsrc, rows, cin, cout, st);
   }
   if (mfma_shape(cin, cout) && x_dt == CFSD_DT_BF16) {
-    rc = bf::launch_dw((const bf16_t*)x, xvm, idx, dpre, dpre_dt, workspace, vsrc, rows, M, cin, cout, st);
+    rc = bf::launch_dw((const bf16_t*)x, xvm, idx, dpre, dpre_dt, workspace, vsrc, rows, (long)batch * rows, cin,
+                       cout, st);
     n_slabs = bf::dw_slabs(batch, rows, cin, cout);
   } else if (cin <= 3 && (cout == 32 || cout == 64) && x_dt == CFSD_DT_F32) {
     const DwGeom g = dw_geom(batch, rows, cin, cout);
     if (g.kind != kDwInMfma) return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight_x: geometry");
-    const bool dbf = CFSD_DT_TYPE(dpre_dt) == CFSD_DT_BF16;
-#define DWIB(CS_, CO_)                                                                             \
-  if (cin == CS_ && cout == CO_) {                                                                 \
-    if (dbf)                                                                                       \
-      hipLaunchKernelGGL((conv_dw_in_mfma<CS_, CO_, bf16_t>), dim3(g.gx), dim3(256), 0, st,        \
-                         (const float*)x, idx, (const bf16_t*)dpre, workspace, vsrc, rows, M, batch, \
-                         xvm, dpvm);                                                               \
-    else                                                                                           \
-      hipLaunchKernelGGL((conv_dw_in_mfma<CS_, CO_, float>), dim3(g.gx), dim3(256), 0, st,         \
-                         (const float*)x, idx, (const float*)dpre, workspace, vsrc, rows, M, batch,  \
-                         xvm, dpvm);                                                               \
-  }
-    DWIB(1, 32) DWIB(2, 32) DWIB(3, 32) DWIB(1, 64) DWIB(2, 64) DWIB(3, 64)
-#undef DWIB
-    rc = launch_status("spiral_conv_bwd_weight_in_bf16");
+    rc = dw_xyz_in((const float*)x, xvm, idx, dpre, dpre_dt, dpvm, workspace, g.gx, vsrc, rows, batch, cin, cout, st);
     n_slabs = g.gx;
   } else {
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight_x: unsupported %d -> %d with dtypes %d/%d", cin,
                      cout, x_dt, dpre_dt);
   }
-  if (rc || !dw) return rc;
-  hipLaunchKernelGGL(slab_reduce, rg, dim3(1024), 0, st, workspace, n_slabs, n_el, dw, cout * kSeq * cin, db);
-  return launch_status("spiral_conv_bwd_weight_x_reduce");
+  if (rc) return rc;
+  return reduce_slabs(!dw, cin, cout, workspace, n_slabs, dw, db, st);
 }
 
 extern "C" int cfsd_spiral_conv_bwd_x(const void* x, int x_dt, const int32_t* idx, const float* dpre,
@@ -3424,43 +3436,20 @@ extern "C" int cfsd_spiral_conv_bwd_x(const void* x, int x_dt, const int32_t* id
                                       int cin, int cout, void* stream) {
   int rc = check_conv_args(x, idx, dpre, batch, vsrc, rows, seq, cin, cout);
   if (rc) return rc;
-  if (!dt_ok(x_dt)) return set_error(CFSD_EINVAL, "spiral_conv_bwd_x: bad x dtype");
-  const bool xbf = CFSD_DT_TYPE(x_dt) == CFSD_DT_BF16;  // x, elu_y and dx share x's storage
+  if ((rc = check_dt("spiral_conv_bwd_x", x_dt))) return rc;  // x, elu_y and dx share x's storage
   if (!dt_ok(dpre_dt) || CFSD_DT_TYPE(dpre_dt) != CFSD_DT_F32)
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_x: dpre must be fp32");
   if (!fused_small(cin, cout))
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_x: small-output layers only (%d -> %d)", cin, cout);
   if (!inv_ptr || !inv_row || !inv_head || !w || !workspace)
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_x: null inverse table / w / workspace");
-  if ((uintptr_t)inv_head & 15) return set_error(CFSD_EINVAL, "inv_head must be 16-B aligned");
-  if ((dw == nullptr) != (db == nullptr))
-    return set_error(CFSD_EINVAL, "dw and db must both be set (or both NULL: deferred)");
-  const size_t need = cfsd_spiral_conv_bwd_workspace(batch, vsrc, rows, seq, cin, cout);
-  if (workspace_bytes < need) return set_error(CFSD_EWORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
-  const hipStream_t st = (hipStream_t)stream;
-  const long Ms = (long)batch * vsrc;
-  const int gx = fused_small_gx(Ms);
-  const int n_el = cout * kSeq * cin + cout;
-#define BOSB(CIN_, CO_)                                                                          \
-  if (cin == CIN_ && cout == CO_) {                                                              \
-    if (xbf)                                                                                     \
-      hipLaunchKernelGGL((conv_bwd_out_mfma<CIN_, CO_, bf16_t>), dim3(gx), dim3(256), 0, st, dpre, \
-                         inv_ptr, inv_row, (const int4*)inv_head, w, (const bf16_t*)elu_y,        \
-                         (const bf16_t*)x, (bf16_t*)dx, workspace, vsrc, rows, Ms, batch,         \
-                         vm_of(x_dt), vm_of(dpre_dt));                                            \
-    else                                                                                         \
-      hipLaunchKernelGGL((conv_bwd_out_mfma<CIN_, CO_, float>), dim3(gx), dim3(256), 0, st, dpre, \
-                         inv_ptr, inv_row, (const int4*)inv_head, w, (const float*)elu_y,         \
-                         (const float*)x, (float*)dx, workspace, vsrc, rows, Ms, batch,           \
-                         vm_of(x_dt), vm_of(dpre_dt));                                            \
-    rc = launch_status("spiral_conv_bwd_small_bf16");                                            \
-    if (rc || !dw) return rc;                                                                    \
-    hipLaunchKernelGGL(slab_reduce, dim3((unsigned)((n_el + 63) / 64)), dim3(1024), 0, st,        \
-                       workspace, gx, n_el, dw, cout * kSeq * cin, db);                          \
-    return launch_status("spiral_conv_bwd_small_reduce");                                        \
-  }
-  BOSB(32, 1) BOSB(32, 2) BOSB(32, 3) BOSB(64, 1) BOSB(64, 2) BOSB(64, 3)
-#undef BOSB
+  if ((rc = check_inv_aligned(inv_head, "inv_head"))) return rc;
+  if ((rc = check_dw_db(dw, db))) return rc;
+  if ((rc = check_workspace(workspace_bytes, cfsd_spiral_conv_bwd_workspace(batch, vsrc, rows, seq, cin, cout))))
+    return rc;
+  rc = bwd_fused_small(x, x_dt, dpre, vm_of(dpre_dt), inv_ptr, inv_row, inv_head, w, elu_y, dx, dw, db, workspace,
+                       batch, vsrc, rows, cin, cout, (hipStream_t)stream);
+  if (rc != kNoShape) return rc;
   return set_error(CFSD_EINVAL, "spiral_conv_bwd_x: unsupported channels %d -> %d", cin, cout);
 }
 
@@ -3479,20 +3468,16 @@ extern "C" int cfsd_spiral_conv_bwd_out_flat(const void* x, int x_dt, const int3
   if (cin != 32 || cout != 3 || vsrc != rows)
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_out_flat: the 32 -> 3 output conv only (%d -> %d)", cin, cout);
   if (!inv_flat || !w || !workspace) return set_error(CFSD_EINVAL, "spiral_conv_bwd_out_flat: null flat / w / workspace");
-  if ((uintptr_t)inv_flat & 15) return set_error(CFSD_EINVAL, "inv_flat must be 16-B aligned");
-  if ((dw == nullptr) != (db == nullptr))
-    return set_error(CFSD_EINVAL, "dw and db must both be set (or both NULL: deferred)");
-  const size_t need = cfsd_spiral_conv_bwd_workspace(batch, vsrc, rows, seq, cin, cout);
-  if (workspace_bytes < need) return set_error(CFSD_EWORKSPACE, "workspace %zu < %zu bytes", workspace_bytes, need);
+  if ((rc = check_inv_aligned(inv_flat, "inv_flat"))) return rc;
+  if ((rc = check_dw_db(dw, db))) return rc;
+  if ((rc = check_workspace(workspace_bytes, cfsd_spiral_conv_bwd_workspace(batch, vsrc, rows, seq, cin, cout))))
+    return rc;
   const hipStream_t st = (hipStream_t)stream;
   const int gx = fused_small_gx((long)batch * vsrc);
   rc = vm32::launch_bwd_out(dpre, inv_flat, flat_width, w, elu_y, x, dx, CFSD_DT_TYPE(x_dt) == CFSD_DT_BF16,
                             workspace, gx, vsrc, rows, batch, st);
-  if (rc || !dw) return rc;
-  const int n_el = cout * kSeq * cin + cout;
-  hipLaunchKernelGGL(slab_reduce, dim3((unsigned)((n_el + 63) / 64)), dim3(1024), 0, st, workspace, gx, n_el, dw,
-                     cout * kSeq * cin, db);
-  return launch_status("spiral_conv_bwd_out_flat_reduce");
+  if (rc) return rc;
+  return reduce_slabs(!dw, cin, cout, workspace, gx, dw, db, st);
 }
 
 // Slab geometry of one deferred weight-gradient item (kind, slab count,

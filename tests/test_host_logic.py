@@ -48,6 +48,106 @@ def test_version_and_error_reporting(lib):
     assert lib.cfsd_spiral_conv_bwd_weight_workspace(16, 17039, 9, 7, 5) == 0
 
 
+def _conv_rejections():
+    """(entry point, defect, arguments, expected code).  Made-up pointers: 64 is
+    non-null and 16-B aligned, 72 misaligned; batch 16, vsrc = rows = 40, seq 9,
+    an ample workspace unless the defect is its size."""
+    P, ODD, WS, TINY = 64, 72, 1 << 40, 64
+    F32, BF16, VM = 0, 1, 0x10
+    B, V, R, S = 16, 40, 40, 9
+
+    def fwd(cin=32, cout=32, act=0, y=P):
+        return [P, P, P, P, y, P, WS, B, V, R, S, cin, cout, act, None]
+
+    def fwd_x(x_dt, y_dt, cin=32, cout=32, w_bf16=P):
+        return [P, x_dt, P, P, w_bf16, P, P, y_dt, B, V, R, S, cin, cout, 0, None]
+
+    def bwd_data(cin=32, cout=32, inv_head=P, seq=S):
+        return [P, P, P, inv_head, P, P, P, P, WS, B, V, R, seq, cin, cout, None]
+
+    def bwd_weight(cin=32, cout=32, db=P, ws=WS):
+        return [P, P, P, P, db, P, ws, B, V, R, S, cin, cout, None]
+
+    def bwd(db=P, ws=WS):
+        return [P, P, P, P, P, P, P, P, P, P, db, P, ws, B, V, R, S, 32, 3, None]
+
+    def bwd_x(dpre_dt=F32, cout=3):
+        return [P, F32, P, P, dpre_dt, P, P, P, P, P, P, P, P, P, WS, B, V, R, S, 32, cout, None]
+
+    def bwd_weight_x(x_dt, dpre_dt, ws=WS):
+        return [P, x_dt, P, P, dpre_dt, P, P, P, ws, B, V, R, S, 32, 32, None]
+
+    def bwd_rowsub(cin=32, flat_width=8, inv_flat=P, ws=WS):
+        return [P, P, P, inv_flat, flat_width, P, P, P, P, P, P, ws, B, V, R, S, cin, 32, None]
+
+    def bwd_data_rowsub(dx_dt=F32, ws=WS):
+        return [P, P, 8, P, P, P, dx_dt, P, ws, B, V, R, S, 32, 32, None]
+
+    def bwd_data_flat(dpre_dt, dx_dt):
+        return [P, dpre_dt, P, 8, P, P, P, dx_dt, B, V, R, S, 32, 32, None]
+
+    def bwd_out_flat(dt, cout=3):
+        return [P, dt, P, P, dt, P, 8, P, P, P, P, P, P, WS, B, V, R, S, 32, cout, None]
+
+    def fwd_in_swap(x_dt=F32, cin=3):
+        return [P, P, P, P, 4, 4, 5, P, x_dt, P, P, P, P, F32, V, R, cin, 32, 0, None]
+
+    return [
+        ("fwd", "48 -> 32", fwd(cin=48), -1),
+        ("fwd", "act 7", fwd(act=7), -1),
+        ("fwd", "null y", fwd(y=None), -1),
+        ("fwd_x", "dtype 2", fwd_x(2, F32), -1),
+        ("fwd_x", "fp32 batch-major 32 -> 32", fwd_x(F32, F32), -1),
+        ("fwd_x", "bf16 vm x, null w_bf16", fwd_x(BF16 | VM, BF16 | VM, w_bf16=None), -1),
+        ("fwd_x", "fp32 vm x with bf16 y", fwd_x(F32 | VM, BF16 | VM), -1),
+        ("fwd_x", "3 -> 16 with bf16 y", fwd_x(F32, BF16, cin=3, cout=16), -1),
+        ("bwd_data", "inv_head at 72", bwd_data(inv_head=ODD), -1),
+        ("bwd_data", "32 -> 5", bwd_data(cout=5), -1),
+        ("bwd_data", "seq 7", bwd_data(seq=7), -1),
+        ("bwd_weight", "dw set, db null", bwd_weight(db=None), -1),
+        ("bwd_weight", "64-byte workspace", bwd_weight(ws=TINY), -2),
+        ("bwd_weight", "7 -> 5", bwd_weight(cin=7, cout=5), -1),
+        ("bwd", "32 -> 3, 64-byte workspace", bwd(ws=TINY), -2),
+        ("bwd", "32 -> 3, dw without db", bwd(db=None), -1),
+        ("bwd_x", "bf16 dpre", bwd_x(dpre_dt=BF16), -1),
+        ("bwd_x", "32 -> 32", bwd_x(cout=32), -1),
+        ("bwd_weight_x", "fp32 vm x with bf16 dpre", bwd_weight_x(F32 | VM, BF16 | VM), -1),
+        ("bwd_weight_x", "bf16 32 -> 32, 64-byte workspace", bwd_weight_x(BF16, BF16, ws=TINY), -2),
+        ("bwd_rowsub", "flat_width 6", bwd_rowsub(flat_width=6), -1),
+        ("bwd_rowsub", "64 -> 32", bwd_rowsub(cin=64), -1),
+        ("bwd_rowsub", "inv_flat at 72", bwd_rowsub(inv_flat=ODD), -1),
+        ("bwd_rowsub", "64-byte workspace", bwd_rowsub(ws=TINY), -2),
+        ("bwd_data_rowsub", "dx dtype 2", bwd_data_rowsub(dx_dt=2), -1),
+        ("bwd_data_rowsub", "64-byte workspace", bwd_data_rowsub(ws=TINY), -2),
+        ("bwd_data_flat", "batch-major operands", bwd_data_flat(F32, F32), -1),
+        ("bwd_data_flat", "fp32 vm dx with bf16 dpre", bwd_data_flat(BF16 | VM, F32 | VM), -1),
+        ("bwd_out_flat", "32 -> 32", bwd_out_flat(F32 | VM, cout=32), -1),
+        ("bwd_out_flat", "batch-major operands", bwd_out_flat(F32), -1),
+        ("fwd_in_swap", "32 -> 32", fwd_in_swap(cin=32), -1),
+        ("fwd_in_swap", "bf16 x", fwd_in_swap(x_dt=BF16), -1),
+    ]
+
+
+def test_conv_entry_points_reject_before_launch(lib):
+    """Every conv entry point validates its arguments before its first launch
+    and keeps its return code: CFSD_EINVAL (-1) for a bad argument,
+    CFSD_EWORKSPACE (-2) for a workspace that is too small."""
+    import torch
+    if torch.cuda.is_available():
+        # a case that a defect lets through would launch on the made-up pointers
+        pytest.skip("made-up pointers: only where no launch can reach a device")
+    cases = _conv_rejections()
+    assert len(cases) == 32
+    for entry, defect, args, want in cases:
+        rc = getattr(lib, "cfsd_spiral_conv_" + entry)(*args)
+        msg = lib.cfsd_last_error_string()
+        assert rc == want, (entry, defect, rc, msg)
+        if defect == "dw set, db null":
+            assert b"dw and db" in msg
+        if entry == "bwd_rowsub" and want == -2:
+            assert b"workspace" in msg
+
+
 def test_inverse_spiral_matches_bruteforce():
     rs = np.random.RandomState(0)
     idx = rs.randint(0, 50, size=(80, 9))
