@@ -30,6 +30,12 @@ SIGNATURES = {
                                        _P]),
     "cfsd_spiral_conv_bwd_weight": (_I, [_P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _P]),
     "cfsd_spiral_conv_bwd_weight_workspace": (_Z, [_I, _I, _I, _I, _I]),
+    "cfsd_spiral_conv_gen_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "cfsd_spiral_conv_gen_bwd_data": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "cfsd_spiral_conv_gen_bwd_weight_workspace": (_Z, [_I, _I, _I, _I, _I]),
+    "cfsd_spiral_conv_gen_bwd_weight": (_I, [_P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _P]),
+    "cfsd_spiral_conv_gen_dw_reduce": (_I, [_P, _Z, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "cfsd_spiral_conv_has_shape": (_I, [_I, _I, _I, _I]),
     "cfsd_spiral_conv_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I,
                                   _I, _I, _I, _P]),
     "cfsd_spiral_conv_bwd_workspace": (_Z, [_I, _I, _I, _I, _I, _I]),

@@ -27,6 +27,10 @@ class Layer:
         self.shape = (b.bsz, self.vsrc, rows, self.seq, cin, cout)
         self.vm = lv in b.xl                         # operands vertex-major ...
         self.bf16 = self.vm and bool(eng.lp_levels)  # ... and bf16
+        # a batch-major layer whose backward the specialised entry points refuse (another spiral
+        # length or channel pair): the general-shape kernels.  They are fp32 batch-major only, so
+        # never a vertex-major layer (vm_levels and the bf16 check admit only shapes with instances)
+        self.general = not self.vm and ops.spiral_conv_bwd_is_general(self.seq, cin, cout, dx=operands[2] is not None)
         enc = key[0] == "enc"
         # Enblock whose input is the previous Enblock's ELU output (else Pool(down)^T follows)
         self.sel_prev = enc and lv > 0 and T.enc_select[lv - 1]
@@ -68,8 +72,23 @@ _bwd_bytes = lambda L: ops.spiral_conv_bwd_workspace(*L.shape)  # noqa: E731
 _rowsub_bytes = lambda L: ops.spiral_conv_bwd_rowsub_workspace(*L.shape)  # noqa: E731
 
 
+_weight_bytes = lambda L: ops.spiral_conv_bwd_weight_workspace(L.bsz, L.rows, L.seq, L.cin, L.cout)  # noqa: E731
+
+
 # kind(L, region, w, wx, ws, x, dpre, dx, elu_y): region = b.ws_dw[key]; w the fp32 weight, wx the
 # weight the vertex-major kernels read (bf16 shadow in bf16 mode); ws = b.ws
+@kind([OUT_KINDS, DEC_KINDS, ENC_KINDS], lambda L, e: L.general, _weight_bytes)
+def general(L, region, w, wx, ws, x, dpre, dx, elu_y):
+    """A shape without a specialised instance (spiral length other than 9, channels outside the
+    lists): dW slabs, then dx, each on the general-shape kernels where the product has no instance
+    (ops routes per product).  Tried first; applies only to a batch-major layer whose backward the
+    specialised entry points refuse, so the plan of every layer they take is unchanged."""
+    d = ops.spiral_conv_bwd_weight(x, L.idx, dpre, None, None, region)
+    if dx is not None:
+        ops.spiral_conv_bwd_data(dpre, L.inv, w, L.vsrc, elu_y=elu_y, out=dx, workspace=ws)
+    return d
+
+
 @kind([OUT_KINDS], lambda L, e: L.vm and L.bsz % 16 == 0 and L.cin == 32 and L.cout == 3 and L.flat is not None,
       _bwd_bytes)
 def out_flat(L, region, w, wx, ws, x, dpre, dx, elu_y):
@@ -152,8 +171,7 @@ def paired(L, region, w, wx, ws, x, dpre, dx, elu_y):
     return ops.spiral_conv_bwd(x, L.idx, dpre, L.inv, w, None, None, dx=dx, elu_y=elu_y, workspace=region)[1]
 
 
-@kind([DEC_KINDS, ENC_KINDS], lambda L, e: True,
-      lambda L: ops.spiral_conv_bwd_weight_workspace(L.bsz, L.rows, L.seq, L.cin, L.cout))
+@kind([DEC_KINDS, ENC_KINDS], lambda L, e: True, _weight_bytes)
 def plain(L, region, w, wx, ws, x, dpre, dx, elu_y):
     """Batch-major fallback: dW slabs, then dx (none at level 0 of the encoder)."""
     d = ops.spiral_conv_bwd_weight(x, L.idx, dpre, None, None, region)

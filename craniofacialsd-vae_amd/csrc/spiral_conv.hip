@@ -2242,6 +2242,26 @@ static bool mfma_shape(int cin, int cout) {
   return (cin == 32 || cin == 64) && (cout == 32 || cout == 64);
 }
 
+template <typename... S>
+static bool in_list(ShapeList<S...>, int cin, int cout) {
+  return ((cin == S::cin && cout == S::cout) || ...);
+}
+// Which shapes the fp32 batch-major entry points take: the lists their
+// dispatch walks (cfsd_spiral_conv_fwd, _bwd_data; dw_f32 behind dw_geom;
+// bwd_fused_small behind cfsd_spiral_conv_bwd and _bwd_x).
+extern "C" int cfsd_spiral_conv_has_shape(int role, int seq, int cin, int cout) {
+  if (seq != kSeq || cin <= 0 || cout <= 0) return 0;
+  const bool mfma = in_list(MfmaShapes{}, cin, cout), xyz_out = in_list(XyzOutShapes{}, cin, cout);
+  const bool xyz_in = in_list(XyzInShapes{}, cin, cout) || in_list(InSmallShapes{}, cin, cout);
+  switch (role) {
+    case CFSD_CONV_FWD: return mfma || xyz_in || xyz_out;
+    case CFSD_CONV_BWD_DATA: return mfma || xyz_out;
+    case CFSD_CONV_BWD_WEIGHT: return mfma || xyz_in || xyz_out;
+    case CFSD_CONV_BWD_FUSED: return in_list(FusedSmallShapes{}, cin, cout);
+    default: return 0;
+  }
+}
+
 // Persistent VALU kernels: one resident round, never more blocks than rows/64.
 template <typename K>
 static unsigned small_grid(K kernel, long rows) {

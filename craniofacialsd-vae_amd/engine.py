@@ -190,6 +190,15 @@ class SDVAEEngine:
         # levels whose tensors are bf16 (the two finest; never the bottleneck)
         self.lp_levels = set()
         if precision == "bf16":
+            for name, lv, cin, cout in self.conv_layers():
+                if lv in (0, 1):  # a bf16 level: the mixed-precision entry points' shapes
+                    gen = not ops.spiral_conv_vm_has_shape(topo.seq[lv], cin, cout)
+                else:             # fp32 batch-major
+                    gen = (not ops.spiral_conv_has_shape(ops.CONV_FWD, topo.seq[lv], cin, cout)
+                           or ops.spiral_conv_bwd_is_general(topo.seq[lv], cin, cout))
+                if gen:
+                    raise ValueError(f"bf16 precision: {name} (spiral length {topo.seq[lv]}, {cin} -> {cout} "
+                                     f"channels) has only the general-shape fp32 kernels; use precision='fp32'")
             if not all(topo.enc_select) or self.spec.n < 3:
                 raise ValueError("bf16 precision needs 0/1 selection down-sampling and >= 3 levels")
             self.lp_levels = {0, 1}
@@ -369,6 +378,13 @@ class SDVAEEngine:
         self.load_optimizer_state_dict(opt["optimizer"])
         return int(last[-11:-3])
 
+    def conv_layers(self):
+        """(parameter name, level, cin, cout) of every SpiralConv."""
+        S = self.spec
+        out = [(f"en_layers.{lv}.conv.layer", lv, cin, cout) for (cin, cout, lv) in S.enc_layers()]
+        out += [(f"de_layers.{i + 1}.conv.layer", lv, cin, cout) for i, (cin, cout, lv, _) in enumerate(S.dec_layers())]
+        return out + [(f"de_layers.{S.n + 1}.layer", 0, S.out_ch[0], S.in_ch)]
+
     # ----------------------------------------------------------- buffers
     def vm_levels(self, bsz):
         """Levels whose 32-channel tensors are stored vertex-major (and routed
@@ -376,10 +392,13 @@ class SDVAEEngine:
         bf16 levels always; in fp32 levels 0 and 1 when the batch is a
         multiple of 16, every down-sampling is a 0/1 selection, and the level's
         convs fit the fp32 vertex-major kernels (32 -> 32/64 with flat
-        inverse lists)."""
+        inverse lists).  None with a spiral length other than 9 at any level:
+        the vertex-major kernels are instances of that length only."""
         if self.lp_levels:
             return set(self.lp_levels)
         T, S = self.topo, self.spec
+        if any(s != 9 for s in T.seq):
+            return set()
         if not (self.vertex_major and bsz % 16 == 0 and all(T.enc_select) and S.n >= 3):
             return set()
         for (cin, cout, lv, _) in S.dec_layers():
@@ -837,7 +856,7 @@ class SDVAEEngine:
     def _flat_dx(self, b, lv, cin, cout):
         """The flat-list bf16 data gradient applies (vertex-major level,
         batch a multiple of 16, 32 -> 32/64 channels, fan-in <= 20)."""
-        return (lv in b.xl and b.bsz % 16 == 0 and cin == 32 and cout in (32, 64)
+        return (lv in b.xl and b.bsz % 16 == 0 and self.topo.seq[lv] == 9 and cin == 32 and cout in (32, 64)
                 and self.topo.spiral_flat[lv] is not None)
 
     def adam_args(self):
@@ -960,7 +979,7 @@ class SDVAEEngine:
         conv evaluated at its kept rows (3 -> 32/64), fp32 input meshes."""
         S, T = self.spec, self.topo
         cin, cout, lv = S.enc_layers()[0]
-        return (self.fuse_swap and lv == 0 and cin == 3 and cout in (32, 64) and T.enc_select[0]
+        return (self.fuse_swap and lv == 0 and T.seq[0] == 9 and cin == 3 and cout in (32, 64) and T.enc_select[0]
                 and data.meshes.dtype == torch.float32 and data.meshes.shape[2] == 3
                 and b.x.dtype == torch.float32 and b.bsz == self.swap_bs ** 2)
 

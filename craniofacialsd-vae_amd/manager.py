@@ -78,6 +78,35 @@ def load_or_build_topology(config, template, precomputed_path):
     return h
 
 
+def check_model_config(model_params):
+    """Refuse, before any precompute, an architecture the kernels cannot run;
+    the ``ValueError`` names the YAML key.  Any spiral length up to
+    ``ops.GEN_MAX_SEQ`` and any channel count up to ``ops.GEN_MAX_CH`` trains
+    (shapes without a specialised kernel take the general-shape ones); the
+    hidden channel counts must be multiples of 4 (the Pool SpMM's rows)."""
+    mp = model_params
+    out_ch = [int(c) for c in mp["out_channels"]]
+    if not out_ch:
+        raise ValueError("model.out_channels is empty")
+    for c in out_ch:
+        if c < 4 or c % 4 or c > ops.GEN_MAX_CH:
+            raise ValueError(f"model.out_channels {out_ch}: every entry must be a multiple of 4 in "
+                             f"[4, {ops.GEN_MAX_CH}], got {c}")
+    if not 1 <= int(mp["in_channels"]) <= ops.GEN_MAX_CH:
+        raise ValueError(f"model.in_channels {mp['in_channels']} outside [1, {ops.GEN_MAX_CH}]")
+    spirals = mp.get("spirals") or {}
+    lengths = [int(n) for n in spirals.get("length", [])]
+    for key, vals in (("length", lengths), ("dilation", spirals.get("dilation") or [])):
+        if len(vals) and len(vals) != len(out_ch):
+            raise ValueError(f"model.spirals.{key} has {len(vals)} entries, model.out_channels {len(out_ch)}")
+    for n in lengths:
+        if not 1 <= n <= ops.GEN_MAX_SEQ:
+            raise ValueError(f"model.spirals.length {lengths}: every entry must lie in [1, {ops.GEN_MAX_SEQ}], got {n}")
+    for d in spirals.get("dilation") or []:
+        if int(d) < 1:
+            raise ValueError(f"model.spirals.dilation {list(spirals['dilation'])}: every entry must be >= 1")
+
+
 class JsonlWriter:
     """``SummaryWriter.add_scalar`` subset writing JSON lines (tensorboard is
     not installed in this image)."""
@@ -105,6 +134,7 @@ class ModelManager(ClassifierStage):
             # model_manager.py:93-94 (assert self._swap_features): the latent
             # consistency loss is defined on swapped bs x bs groups only
             raise ValueError("latent_consistency_weight > 0 needs data.swap_features: True")
+        check_model_config(self._model_params)
         self.template = precompute.load_template(configurations["data"]["template_path"])
         self.topology_arrays = load_or_build_topology(configurations, self.template, precomputed_storage_path)
         self.topology = topology.DeviceTopology.from_npz(self.topology_arrays, device=self.device)

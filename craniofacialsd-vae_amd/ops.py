@@ -105,7 +105,50 @@ def _out(out, shape, like, name="out"):
 
 
 # ------------------------------------------------------------------ spiral conv
+CONV_FWD, CONV_BWD_DATA, CONV_BWD_WEIGHT, CONV_BWD_FUSED = 0, 1, 2, 3  # CFSD_CONV_*: roles of spiral_conv_has_shape
+GEN_MAX_SEQ, GEN_MAX_CH = 32, 512                   # CFSD_GEN_MAX_SEQ, CFSD_GEN_MAX_CH
+
+
+def spiral_conv_has_shape(role, seq, cin, cout):
+    """True when the specialised fp32 batch-major kernels of ``role`` (CONV_FWD,
+    CONV_BWD_DATA, CONV_BWD_WEIGHT) have an instance for this shape; any other
+    shape inside the limits takes the general-shape entry points
+    (``cfsd_spiral_conv_gen_*``).  CONV_BWD_FUSED: a small-output layer
+    (32 / 64 -> 1, 2, 3) whose dx + dW ``cfsd_spiral_conv_bwd`` / ``_bwd_x``
+    run as one fused launch."""
+    return bool(_abi.lib().cfsd_spiral_conv_has_shape(int(role), int(seq), int(cin), int(cout)))
+
+
+def spiral_conv_bwd_is_general(seq, cin, cout, dx=True):
+    """True when ``cfsd_spiral_conv_bwd`` refuses the shape, so the backward
+    (dW, and dx unless ``dx`` is False: the first Enblock) is two launches with
+    the general kernels wherever a product has no instance.  The library takes
+    the fused small-output layers, and any shape its dW and (with dx) its dx
+    entry points both have."""
+    if spiral_conv_has_shape(CONV_BWD_FUSED, seq, cin, cout):
+        return False
+    roles = (CONV_BWD_WEIGHT,) + ((CONV_BWD_DATA,) if dx else ())
+    return not all(spiral_conv_has_shape(r, seq, cin, cout) for r in roles)
+
+
+def spiral_conv_vm_has_shape(seq, cin, cout):
+    """True when the vertex-major / mixed-precision entry points (``_fwd_x``,
+    ``_bwd_weight_x``, ``_bwd_x``) have instances for a layer of this shape:
+    the MFMA shapes, the xyz input conv, the fused small-output layers.  The
+    general kernels are batch-major fp32 only, so nothing else can run
+    vertex-major or in bf16."""
+    return (spiral_conv_has_shape(CONV_BWD_WEIGHT, seq, cin, cout)
+            or spiral_conv_has_shape(CONV_BWD_FUSED, seq, cin, cout))
+
+
+def _check_gen_limits(seq, cin, cout):
+    if not (1 <= seq <= GEN_MAX_SEQ and 1 <= cin <= GEN_MAX_CH and 1 <= cout <= GEN_MAX_CH):
+        raise ValueError(f"SpiralConv of spiral length {seq}, {cin} -> {cout} channels is outside the "
+                         f"general kernels' limits (length <= {GEN_MAX_SEQ}, channels <= {GEN_MAX_CH})")
+
+
 def spiral_conv_workspace(bsz, vsrc, rows, seq, cin, cout):
+    """Workspace of the specialised forward / dx kernels (0 for a shape without one)."""
     return int(_abi.lib().cfsd_spiral_conv_workspace(bsz, vsrc, rows, seq, cin, cout))
 
 
@@ -119,8 +162,10 @@ def _conv_ws(workspace, device, need):
     return workspace, nbytes
 
 
-def spiral_conv_fwd(x, idx, w, b, act=ACT_NONE, out=None, workspace=None):
-    """y[b, r] = act(b + W . concat_s x[b, idx[r, s]])  (model.py:27-41)."""
+def spiral_conv_fwd(x, idx, w, b, act=ACT_NONE, out=None, workspace=None, general=False):
+    """y[b, r] = act(b + W . concat_s x[b, idx[r, s]])  (model.py:27-41).
+    A shape without a specialised instance takes the general-shape kernel;
+    ``general=True`` forces it (tests, tools/bench_general_conv.py)."""
     bsz, vsrc, cin = x.shape
     rows, seq = idx.shape
     cout = w.shape[0]
@@ -130,15 +175,21 @@ def spiral_conv_fwd(x, idx, w, b, act=ACT_NONE, out=None, workspace=None):
     if b is not None:
         _need(b, (cout,), name="bias")
     y = _out(out, (bsz, rows, cout), x)
+    if general or not spiral_conv_has_shape(CONV_FWD, seq, cin, cout):  # no instance: the general kernel
+        _check_gen_limits(seq, cin, cout)
+        call("cfsd_spiral_conv_gen_fwd", ptr(x), ptr(idx), ptr(w), ptr(b), ptr(y), bsz, vsrc, rows, seq, cin, cout,
+             act, stream_ptr())
+        return y
     ws, nb = _conv_ws(workspace, x.device, spiral_conv_workspace(bsz, vsrc, rows, seq, cin, cout))
     call("cfsd_spiral_conv_fwd", ptr(x), ptr(idx), ptr(w), ptr(b), ptr(y), ptr(ws),
          ctypes.c_size_t(nb), bsz, vsrc, rows, seq, cin, cout, act, stream_ptr())
     return y
 
 
-def spiral_conv_bwd_data(dpre, inv, w, vsrc, elu_y=None, out=None, workspace=None):
+def spiral_conv_bwd_data(dpre, inv, w, vsrc, elu_y=None, out=None, workspace=None, general=False):
     """dx[b, u] = g * sum_{(r,s) in inv(u)} W_s^T dpre[b, r]; ``inv`` is the
-    (inv_ptr, inv_row, inv_head) triple of ``topology.inverse_spiral``."""
+    (inv_ptr, inv_row, inv_head) triple of ``topology.inverse_spiral``.
+    ``general``: as :func:`spiral_conv_fwd`."""
     bsz, rows, cout = dpre.shape
     inv_ptr, inv_row, inv_head = inv
     seq = (inv_ptr.numel() - 1) // vsrc
@@ -151,6 +202,11 @@ def spiral_conv_bwd_data(dpre, inv, w, vsrc, elu_y=None, out=None, workspace=Non
     if elu_y is not None:
         _need(elu_y, (bsz, vsrc, cin), name="elu_y")
     dx = _out(out, (bsz, vsrc, cin), dpre)
+    if general or not spiral_conv_has_shape(CONV_BWD_DATA, seq, cin, cout):  # no instance: the general kernel
+        _check_gen_limits(seq, cin, cout)
+        call("cfsd_spiral_conv_gen_bwd_data", ptr(dpre), ptr(inv_ptr), ptr(inv_row), ptr(w), ptr(elu_y), ptr(dx),
+             bsz, vsrc, rows, seq, cin, cout, stream_ptr())
+        return dx
     ws, nb = _conv_ws(workspace, dpre.device, spiral_conv_workspace(bsz, vsrc, rows, seq, cin, cout))
     call("cfsd_spiral_conv_bwd_data", ptr(dpre), ptr(inv_ptr), ptr(inv_row), ptr(inv_head), ptr(w),
          ptr(elu_y), ptr(dx), ptr(ws), ctypes.c_size_t(nb), bsz, vsrc, rows, seq, cin, cout,
@@ -158,14 +214,20 @@ def spiral_conv_bwd_data(dpre, inv, w, vsrc, elu_y=None, out=None, workspace=Non
     return dx
 
 
-def spiral_conv_bwd_weight_workspace(bsz, rows, seq, cin, cout):
+def spiral_conv_bwd_weight_workspace(bsz, rows, seq, cin, cout, general=False):
+    if general or not spiral_conv_has_shape(CONV_BWD_WEIGHT, seq, cin, cout):
+        return int(_abi.lib().cfsd_spiral_conv_gen_bwd_weight_workspace(bsz, rows, seq, cin, cout))
     return int(_abi.lib().cfsd_spiral_conv_bwd_weight_workspace(bsz, rows, seq, cin, cout))
 
 
-def spiral_conv_bwd_weight(x, idx, dpre, dw, db, workspace):
+def spiral_conv_bwd_weight(x, idx, dpre, dw, db, workspace, general=False):
     """dW/db of one SpiralConv.  With ``dw is db is None`` the reduction is
     deferred: the partials stay in ``workspace`` and a DeferredDw descriptor
-    is returned for ``dw_reduce_batch`` (which must get the real dw/db)."""
+    is returned for ``dw_reduce_batch`` (which must get the real dw/db).  A
+    shape without a specialised instance takes the general kernel; its deferred
+    slabs (:class:`DeferredGenDw`) are reduced by ``spiral_conv_gen_dw_reduce``
+    or as an item of ``dw_reduce_batch``, which reduces them in a launch of
+    their own before the batched one.  ``general``: as :func:`spiral_conv_fwd`."""
     bsz, vsrc, cin = x.shape
     rows, seq = idx.shape
     cout = dpre.shape[2]
@@ -176,10 +238,15 @@ def spiral_conv_bwd_weight(x, idx, dpre, dw, db, workspace):
         _need(dw, (cout, seq * cin), name="dw")
         _need(db, (cout,), name="db")
     _need(workspace, None, name="workspace")
-    need = spiral_conv_bwd_weight_workspace(bsz, rows, seq, cin, cout)
+    need = spiral_conv_bwd_weight_workspace(bsz, rows, seq, cin, cout, general)
     nbytes = workspace.numel() * workspace.element_size()
     if nbytes < need:
         raise ValueError(f"workspace {nbytes} < {need} bytes")
+    if general or not spiral_conv_has_shape(CONV_BWD_WEIGHT, seq, cin, cout):  # no instance: the general kernel
+        _check_gen_limits(seq, cin, cout)
+        call("cfsd_spiral_conv_gen_bwd_weight", ptr(x), ptr(idx), ptr(dpre), ptr(dw), ptr(db), ptr(workspace),
+             ctypes.c_size_t(nbytes), bsz, vsrc, rows, seq, cin, cout, stream_ptr())
+        return DeferredGenDw(workspace, bsz, rows, seq, cin, cout) if dw is None else None
     call("cfsd_spiral_conv_bwd_weight", ptr(x), ptr(idx), ptr(dpre), ptr(dw), ptr(db),
          ptr(workspace), ctypes.c_size_t(nbytes), bsz, vsrc, rows, seq, cin, cout, stream_ptr())
     if dw is None:
@@ -200,12 +267,40 @@ class DeferredDw:
         return _abi.DwSlabs(self.workspace.data_ptr(), dw.data_ptr(), db.data_ptr(), *self.sizes)
 
 
+class DeferredGenDw:
+    """Slab set left by a deferred general-shape weight gradient
+    (``cfsd_spiral_conv_gen_bwd_weight`` with dw = db = NULL)."""
+
+    def __init__(self, workspace, batch, rows, seq, cin, cout):
+        self.workspace = workspace
+        self.sizes = (batch, rows, seq, cin, cout)
+
+
+def spiral_conv_gen_dw_reduce(d, dw, db):
+    """Second stage of a deferred general-shape weight gradient: the slabs of
+    ``d`` (:class:`DeferredGenDw`) summed into dw / db, bit-identical to the
+    immediate form."""
+    bsz, rows, seq, cin, cout = d.sizes
+    _need(dw, (cout, seq * cin), name="dw")
+    _need(db, (cout,), name="db")
+    nbytes = d.workspace.numel() * d.workspace.element_size()
+    call("cfsd_spiral_conv_gen_dw_reduce", ptr(d.workspace), ctypes.c_size_t(nbytes), ptr(dw), ptr(db), bsz, rows,
+         seq, cin, cout, stream_ptr())
+
+
 def dw_reduce_batch(items, adam=None):
     """Reduce several deferred weight gradients in ONE launch.
     ``items``: list of (DeferredDw, dw, db).  ``adam``: optional dict(param,
     grad, m, v, step, lr, beta1, beta2, eps, weight_decay, shadow) -- the Adam
     step over the whole flat buffers fused into the same launch (the items'
     dw/db must be views of ``grad``)."""
+    # general-shape slab sets are not items of the batched launch: each is reduced into its
+    # dw / db first, so with ``adam`` the batched launch's rest workgroups update those elements
+    gen = [it for it in items if isinstance(it[0], DeferredGenDw)]
+    if gen:
+        for d, dw, db in gen:
+            spiral_conv_gen_dw_reduce(d, dw, db)
+        items = [it for it in items if not isinstance(it[0], DeferredGenDw)]
     if not items and adam is None:
         return
     arr = (_abi.DwSlabs * max(len(items), 1))(*[d.desc(dw, db) for d, dw, db in items])
@@ -225,6 +320,9 @@ def dw_reduce_batch(items, adam=None):
 
 
 def spiral_conv_bwd_workspace(bsz, vsrc, rows, seq, cin, cout):
+    if spiral_conv_bwd_is_general(seq, cin, cout, dx=False):  # no fused launch, no dW instance: the general
+        return spiral_conv_bwd_weight_workspace(bsz, rows, seq, cin, cout)  # dW slabs (the general dx needs none)
+    # the library's own query; it also covers a specialised dW followed by the general dx
     return int(_abi.lib().cfsd_spiral_conv_bwd_workspace(bsz, vsrc, rows, seq, cin, cout))
 
 
@@ -254,6 +352,12 @@ def spiral_conv_bwd(x, idx, dpre, inv, w, dw, db, dx=None, elu_y=None, workspace
         _need(dx, (bsz, vsrc, cin), name="dx")
     if elu_y is not None:
         _need(elu_y, (bsz, vsrc, cin), name="elu_y")
+    if spiral_conv_bwd_is_general(seq, cin, cout, dx=dx is not None):  # the library refuses: two launches
+        ws, _ = _conv_ws(workspace, x.device, spiral_conv_bwd_workspace(bsz, vsrc, rows, seq, cin, cout))
+        if dx is not None:
+            spiral_conv_bwd_data(dpre, inv, w, vsrc, elu_y=elu_y, out=dx)
+        d = spiral_conv_bwd_weight(x, idx, dpre, dw, db, ws)
+        return (dx, d) if dw is None else dx
     ws, nb = _conv_ws(workspace, x.device, spiral_conv_bwd_workspace(bsz, vsrc, rows, seq, cin, cout))
     call("cfsd_spiral_conv_bwd", ptr(x), ptr(idx), ptr(dpre), ptr(inv_ptr), ptr(inv_row),
          ptr(inv_head), ptr(w), ptr(elu_y), ptr(dx), ptr(dw), ptr(db), ptr(ws), ctypes.c_size_t(nb),

@@ -244,6 +244,57 @@ int cfsd_spiral_conv_bwd_data_rowsub(const float* dpre, const int32_t* inv_flat,
 int cfsd_spiral_gather(const float* x, const int32_t* idx, float* g, int batch, int vsrc, int rows,
                        int seq, int cin, void* stream);
 
+/* General-shape SpiralConv (ABI 4.19): the three products above for ANY
+ * 1 <= seq <= CFSD_GEN_MAX_SEQ and 1 <= cin, cout <= CFSD_GEN_MAX_CH, fp32,
+ * batch-major, on the fp32 MFMA, deterministic (fixed summation orders, no
+ * atomics).  The entry points above are template instances of a few shapes
+ * (spiral length 9, channels from {1, 2, 3, 16, 32, 64}) and refuse the rest;
+ * cfsd_spiral_conv_has_shape says which, and these take whatever they refuse
+ * (and, untuned, what they take).  Semantics and operand shapes exactly as
+ * documented for cfsd_spiral_conv_fwd / _bwd_data / _bwd_weight; `rows` may be
+ * a subset.  Sizes beyond the limits, and tensors or tables of 2^31 or more
+ * elements, are refused with CFSD_EINVAL before any launch. */
+#define CFSD_GEN_MAX_SEQ 32
+#define CFSD_GEN_MAX_CH 512
+int cfsd_spiral_conv_gen_fwd(const float* x, const int32_t* idx, const float* w, const float* bias,
+                             float* y, int batch, int vsrc, int rows, int seq, int cin, int cout,
+                             int act, void* stream);
+/* dx through the (u, s)-keyed inverse CSR alone (no inv_head, no workspace):
+ * the dpre rows of list (u, s) are added in list order, the sums contracted
+ * with the slot's weights in ascending s.  A source vertex with no entry gets
+ * exactly 0. */
+int cfsd_spiral_conv_gen_bwd_data(const float* dpre, const int32_t* inv_ptr, const int32_t* inv_row,
+                                  const float* w, const float* elu_y, float* dx, int batch, int vsrc,
+                                  int rows, int seq, int cin, int cout, void* stream);
+/* dw, db by a two-stage reduction of fixed order: the batch * rows rows are
+ * cut into chunks, chunk p's sums (rows ascending) go to slab p of
+ * `workspace` (cfsd_spiral_conv_gen_bwd_weight_workspace() bytes; 0 = sizes
+ * outside the limits), and each element's slabs are added in a fixed order.
+ * dw == db == NULL defers the second stage: the slabs stay in `workspace`
+ * until cfsd_spiral_conv_gen_dw_reduce (same sizes) adds them, with the same
+ * result bit for bit.  These slabs are NOT items of cfsd_dw_reduce_batch; a
+ * step that ends in cfsd_dw_reduce_batch_adam reduces them into the flat
+ * gradient first, and that launch's rest workgroups apply Adam to them. */
+size_t cfsd_spiral_conv_gen_bwd_weight_workspace(int batch, int rows, int seq, int cin, int cout);
+int cfsd_spiral_conv_gen_bwd_weight(const float* x, const int32_t* idx, const float* dpre, float* dw,
+                                    float* db, float* workspace, size_t workspace_bytes, int batch,
+                                    int vsrc, int rows, int seq, int cin, int cout, void* stream);
+int cfsd_spiral_conv_gen_dw_reduce(const float* workspace, size_t workspace_bytes, float* dw, float* db,
+                                   int batch, int rows, int seq, int cin, int cout, void* stream);
+/* 1 when the fp32 batch-major entry point of `role` (cfsd_spiral_conv_fwd,
+ * _bwd_data, _bwd_weight) has a kernel instance for this shape, else 0 (also
+ * for an unknown role or a non-positive size).  CFSD_CONV_BWD_FUSED: the
+ * shape is a small-output layer whose dx + dW cfsd_spiral_conv_bwd and
+ * cfsd_spiral_conv_bwd_x run as one fused launch (32 / 64 -> 1, 2, 3), whether
+ * or not _bwd_data / _bwd_weight have it on their own.  cfsd_spiral_conv_bwd
+ * takes a shape when this role is 1, or _bwd_weight's is and (without dx, or)
+ * _bwd_data's is. */
+#define CFSD_CONV_FWD 0
+#define CFSD_CONV_BWD_DATA 1
+#define CFSD_CONV_BWD_WEIGHT 2
+#define CFSD_CONV_BWD_FUSED 3
+int cfsd_spiral_conv_has_shape(int role, int seq, int cin, int cout);
+
 /* ---------------------------------------------------------------- Pool
  * Replaces Pool (model.py:50-55: index_select * value, torch_scatter.scatter_add)
  * and its autograd, as a row-sorted CSR SpMM whose per-row order is the COO
