@@ -6,146 +6,96 @@ fallback for any kernel.
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CFSD_LIB_PATH") or os.path.join(_HERE, "libcfsd.so")
 
+HEADER_PATH = os.environ.get("CFSD_HEADER_PATH") or os.path.join(os.path.dirname(_HERE), "include", "cfsd.h")
+
 _lib = None
-
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-_F = ctypes.c_float
-_Z = ctypes.c_size_t
-_U64 = ctypes.c_ulonglong
-
-# name -> (restype, argtypes); must match include/cfsd.h exactly.
-SIGNATURES = {
-    "cfsd_version": (_I, []),
-    "cfsd_last_error_string": (ctypes.c_char_p, []),
-    "cfsd_spiral_conv_workspace": (_Z, [_I, _I, _I, _I, _I, _I]),
-    "cfsd_spiral_conv_fwd": (_I, [_P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spiral_conv_bwd_data": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I,
-                                       _P]),
-    "cfsd_spiral_conv_bwd_weight": (_I, [_P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spiral_conv_bwd_weight_workspace": (_Z, [_I, _I, _I, _I, _I]),
-    "cfsd_spiral_conv_gen_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spiral_conv_gen_bwd_data": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spiral_conv_gen_bwd_weight_workspace": (_Z, [_I, _I, _I, _I, _I]),
-    "cfsd_spiral_conv_gen_bwd_weight": (_I, [_P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spiral_conv_gen_dw_reduce": (_I, [_P, _Z, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spiral_conv_has_shape": (_I, [_I, _I, _I, _I]),
-    "cfsd_spiral_conv_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I,
-                                  _I, _I, _I, _P]),
-    "cfsd_spiral_conv_bwd_workspace": (_Z, [_I, _I, _I, _I, _I, _I]),
-    "cfsd_spiral_conv_bwd_paired": (_I, [_I, _I, _I, _I, _I, _I]),
-    "cfsd_spiral_conv_bwd_rowsub": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I,
-                                         _I, _I, _I, _P]),
-    "cfsd_spiral_conv_bwd_rowsub_x": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I,
-                                           _I, _I, _I, _P]),
-    "cfsd_spiral_conv_bwd_rowsub_workspace": (_Z, [_I, _I, _I, _I, _I, _I]),
-    "cfsd_spiral_conv_bwd_flat_pair": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I,
-                                            _I, _I, _P]),
-    "cfsd_spiral_conv_bwd_flat_pair_workspace": (_Z, [_I, _I, _I, _I, _I]),
-    "cfsd_spiral_conv_bwd_flat_pair_bf16": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I,
-                                                 _P]),
-    "cfsd_spiral_conv_bwd_rowsub_pair_bf16": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I,
-                                                   _I, _P]),
-    "cfsd_spiral_conv_bwd_data_rowsub": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _Z, _I, _I, _I, _I, _I, _I,
-                                              _P]),
-    "cfsd_spiral_conv_bwd_data_rowsub_workspace": (_Z, [_I, _I, _I, _I]),
-    "cfsd_linear_bwd_split_parts": (_I, [_I]),
-    "cfsd_bottleneck_bwd_exchange_floats": (_Z, [_I, _I, _I, _I]),
-    "cfsd_linear_bwd_split": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfsd_latent_bwd_parts": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spiral_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spmm_csr_sched": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spmm_csr": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfsd_swap_features": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cfsd_swap_features_x": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spiral_conv_fwd_up_supported": (_I, [_I, _I, _I, _I, _I]),
-    "cfsd_spiral_conv_fwd_up": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_gather_meshes": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cfsd_normalize": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfsd_spectral_blend": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfsd_linear_workspace": (_Z, [_I, _I, _I]),
-    "cfsd_linear_fwd": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _P]),
-    "cfsd_linear_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
-    "cfsd_recon_lap_blocks": (_I, [_I, _I]),
-    "cfsd_recon_lap_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfsd_recon_lap_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
-    "cfsd_recon_lap_bwd_finalize": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _I, _P, _P,
-                                         _P, _F, _F, _P]),
-    "cfsd_recon_lap_fwd_x": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfsd_recon_lap_bwd_x": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P]),
-    "cfsd_recon_lap_bwd_finalize_x": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _I, _P, _P,
-                                           _P, _F, _F, _I, _P]),
-    "cfsd_latent_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P]),
-    "cfsd_latent_linear_fwd_supported": (_I, [_I, _I, _I]),
-    "cfsd_latent_linear_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F,
-                                    _P, _P, _P, _I, _P]),
-    "cfsd_latent_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cfsd_loss_finalize": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _F, _F, _F, _P]),
-    "cfsd_adam": (_I, [_P, _P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _P, _P]),
-    "cfsd_adam_scaled": (_I, [_P, _P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _F, _P, _P]),
-    "cfsd_spiral_conv_fwd_in_swap": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I,
-                                          _I, _P]),
-    "cfsd_bottleneck_bwd": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I,
-                                 _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P]),
-    "cfsd_spiral_conv_fwd_x": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spiral_conv_bwd_data_x": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spiral_conv_bwd_data_flat": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spiral_conv_bwd_weight_x_workspace": (_Z, [_I, _I, _I, _I, _I]),
-    "cfsd_spiral_conv_bwd_weight_x": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spiral_conv_bwd_x": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I,
-                                    _I, _I, _I, _P]),
-    "cfsd_spiral_conv_bwd_out_flat": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I,
-                                           _I, _I, _I, _P]),
-    "cfsd_spmm_csr_x": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spmm_uniform": (_I, [_I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cfsd_spmm_sched_csr": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "cfsd_cast": (_I, [_P, _I, _P, _I, _Z, _P]),
-    "cfsd_step_begin": (_I, [_P, _U64, _P, _I, _P, _I, _P, _I, _I, _P, _I, _I, _P, _P]),
-    "cfsd_dw_reduce_batch": (_I, [_P, _I, _P]),
-    "cfsd_dw_reduce_batch_adam": (_I, [_P, _I, _P, _P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _P, _P]),
-    "cfsd_scale": (_I, [_P, _Z, _F, _P]),
-    "cfsd_elu_bwd": (_I, [_P, _P, _P, _Z, _P]),
-    "cfsd_vertex_errors": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
-    "cfsd_group_vertex_errors": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),
-    "cfsd_region_means": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfsd_nn_points_workspace": (_Z, [_I, _I, _I]),
-    "cfsd_nn_points": (_I, [_P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P]),
-    "cfsd_chamfer_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "cfsd_point_face_workspace": (_Z, [_I, _I]),
-    "cfsd_point_face": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_point_face_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_raster_workspace": (_Z, [_I, _I]),
-    "cfsd_vertex_normals": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "cfsd_render_vertices": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F,
-                                  _F, _P]),
-    "cfsd_rasterize": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P]),
-    "cfsd_interpolate_colors": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _P]),
-    "cfsd_class_stats_workspace": (_Z, [_I, _I, _I]),
-    "cfsd_class_stats": (_I, [_P, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _I, _P]),
-    "cfsd_discriminant_scores": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "cfsd_mlp_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
-    "cfsd_mlp_workspace": (_Z, [_P, _I, _I]),
-    "cfsd_mlp_train_steps": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F,
-                                  _F, _F, _P]),
-    "cfsd_mlp_head_step": (_I, [_P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _I, _F, _P, _I, _I, _I,
-                                _F, _F, _F, _F, _F, _P]),
-}
-
-
-class DwSlabs(ctypes.Structure):
-    """``cfsd_dw_slabs`` (include/cfsd.h): one deferred weight-gradient slab set."""
-    _fields_ = [("workspace", _P), ("dw", _P), ("db", _P), ("batch", _I), ("vsrc", _I),
-                ("rows", _I), ("cin", _I), ("cout", _I), ("fused", _I)]
 
 
 class CfsdError(RuntimeError):
     pass
+
+
+# ---------------------------------------------------------------- the ABI, read from cfsd.h
+# The header is the one statement of the ABI: the prototypes, cfsd_dw_slabs and the integer
+# CFSD_* constants below are parsed from its text.  The parser knows the few C types the
+# header uses and refuses (CfsdError naming the declaration) whatever it does not know.
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
+            "unsigned long long": ctypes.c_ulonglong}
+_RETURNS = {**_SCALARS, "const char *": ctypes.c_char_p}
+_PROTO = re.compile(r"([\w\s*]+?)\b(cfsd_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+_STRUCT = re.compile(r"typedef\s+struct\s*\{([^{}]*)\}\s*(\w+)\s*;")
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(CFSD_\w+)(\(?)(.*)$", re.M)
+
+
+def _ctype(decl, where):
+    """ctypes type of one parameter or field (``type [name]``): any pointer is a c_void_p."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if "*" in words and "[" not in decl:
+        return ctypes.c_void_p
+    for ty in (" ".join(words), " ".join(words[:-1])):
+        if ty in _SCALARS and "[" not in decl:
+            return _SCALARS[ty]
+    raise CfsdError(f"cfsd.h: {where}: unsupported type in '{' '.join(decl.split())}'")
+
+
+def _fields(body, where):
+    """ctypes ``_fields_`` of a struct body; one declaration may name several scalar fields."""
+    out = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        first, *more = (d.strip() for d in decl.split(","))
+        names = [first.replace("*", " ").split()[-1], *more]
+        if not all(re.fullmatch(r"[A-Za-z_]\w*", n) for n in names) or (more and "*" in decl):
+            raise CfsdError(f"cfsd.h: {where}: cannot read the field declaration '{decl}'")
+        out += [(n, _ctype(first, where)) for n in names]
+    return out
+
+
+def parse_header(text):
+    """(signatures {name: (restype, [argtypes])}, structs {name: _fields_}, constants {CFSD_X: int})."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S).replace("\\\n", " ")
+    constants = {}
+    for name, call, body in _DEFINE.findall(text):
+        if call or not body.strip():  # function-like macro / include guard
+            continue
+        m = re.fullmatch(r"\(\s*(-?\w+)\s*\)|(-?\w+)", body.strip())
+        try:
+            constants[name] = int(m.group(1) or m.group(2), 0)
+        except (AttributeError, ValueError):
+            raise CfsdError(f"cfsd.h: #define {name} {body.strip()}: not an integer constant") from None
+    code = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    structs = {name: _fields(body, name) for body, name in _STRUCT.findall(code)}
+    signatures = {}
+    for ret, name, params in _PROTO.findall(_STRUCT.sub("", code)):
+        ret = " ".join(ret.replace("*", " * ").split())
+        if ret not in _RETURNS:
+            raise CfsdError(f"cfsd.h: {name}: unsupported return type '{ret}'")
+        params = [p.strip() for p in params.split(",")]
+        signatures[name] = (_RETURNS[ret], [] if params == ["void"] else [_ctype(p, name) for p in params])
+    # a declaration the prototype pattern cannot consume must not drop out silently
+    seen = re.findall(r"(cfsd_[a-z0-9_]+)\s*\(", code)
+    if len(seen) != len(signatures):
+        lost = sorted(set(seen) - set(signatures)) or sorted(n for n in set(seen) if seen.count(n) > 1)
+        raise CfsdError(f"cfsd.h: {len(seen)} cfsd_*( declarations but {len(signatures)} prototypes read: {lost}")
+    return signatures, structs, constants
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        SIGNATURES, _structs, CONSTANTS = parse_header(_f.read())
+except OSError as e:
+    raise CfsdError(f"cannot read the C ABI from {HEADER_PATH} (set CFSD_HEADER_PATH): {e}") from None
+if "cfsd_dw_slabs" not in _structs:
+    raise CfsdError(f"{HEADER_PATH}: no 'typedef struct {{ ... }} cfsd_dw_slabs;' found")
+DwSlabs = type("DwSlabs", (ctypes.Structure,), {
+    "__doc__": "``cfsd_dw_slabs`` (include/cfsd.h): one deferred weight-gradient slab set.",
+    "_fields_": _structs["cfsd_dw_slabs"]})
 
 
 def load(path=LIB_PATH):

@@ -42,8 +42,8 @@
 
 namespace cfsd {
 
-constexpr int kClsMaxD = 128;
-constexpr int kClsMaxC = 64;
+constexpr int kClsMaxD = CFSD_CLS_MAX_D;
+constexpr int kClsMaxC = CFSD_CLS_MAX_CLASSES;
 constexpr int kStatRows = 64;         // rows per staged chunk: one wave ballots their labels
 constexpr int kStatThreads = 256;
 constexpr int kStatSliceRows = 2048;  // least rows worth a slice of their own
@@ -237,9 +237,9 @@ __global__ __launch_bounds__(kDsThreads) void discriminant_k(const float* __rest
 }
 
 // ------------------------------------------------------------ MLP
-constexpr int kMlpMaxLayers = 6;
-constexpr int kMlpMaxWidth = 1024;
-constexpr int kMlpMaxBs = 16;
+constexpr int kMlpMaxLayers = CFSD_MLP_MAX_LAYERS;
+constexpr int kMlpMaxWidth = CFSD_MLP_MAX_WIDTH;
+constexpr int kMlpMaxBs = CFSD_MLP_MAX_BS;
 constexpr int kMlpFwdThreads = 512;
 constexpr int kMlpStepThreads = 1024;
 constexpr size_t kMlpLdsMax = 159 * 1024;

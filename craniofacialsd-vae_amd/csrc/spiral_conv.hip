@@ -1291,7 +1291,7 @@ struct DwRedItem {
   float* db;
   int kind, cin, cout, n_slabs, n_el, blk0;
 };
-constexpr int kMaxDwRed = 16;
+constexpr int kMaxDwRed = CFSD_DW_REDUCE_MAX;
 // Optional Adam step fused into the reduction (single-process training: no
 // gradient exchange between the reduce and the update).  Every reduced
 // element is updated by the thread that produced its gradient; the elements
@@ -2769,7 +2769,7 @@ static int dw_xyz_in(const float* x, int xvm, const int* idx, const void* dpre, 
 }
 
 constexpr int kDwVm32 = 1;  // 32 -> 32 with vertex-major x and dpre: vm32::conv_dw_vm32
-// The fp32 weight gradient takes vm32::conv_dw_vm32 (its slabs: cfsd_dw_slabs.fused == 3)
+// The fp32 weight gradient takes vm32::conv_dw_vm32 (its slabs: cfsd_dw_slabs.fused == CFSD_DW_VM32)
 static bool dw_vm32_path(int xvm, int dpvm, int cin, int cout, int batch) {
   return kDwVm32 && xvm && dpvm && cin == 32 && cout == 32 && batch % 16 == 0;
 }
@@ -3349,7 +3349,7 @@ extern "C" int cfsd_spiral_conv_bwd_flat_pair(const float* x, const int32_t* idx
   hipStream_t st = (hipStream_t)stream;
   const DwGeom g = dw_geom(batch, rows, cin, cout);
   float* ws_db = workspace + (size_t)g.gx * dw_units(cin, cout) * 1024;
-  const int nslab = vm32::dw_slabs(batch, rows, g.gx);  // as cfsd_dw_reduce_batch's fused = 3 items
+  const int nslab = vm32::dw_slabs(batch, rows, g.gx);  // as cfsd_dw_reduce_batch's fused = CFSD_DW_VM32 items
   rc = vm32::launch_bwd_vm_pair(dpre, inv_flat, flat_width, w, elu_y, dx, x, idx, workspace, ws_db, nslab, vsrc,
                                 rows, batch, st);
   if (rc) return rc;
@@ -3371,7 +3371,7 @@ extern "C" int cfsd_spiral_conv_bwd_rowsub_pair_bf16(const void* x, const int32_
   if ((rc = check_flat_width("spiral_conv_bwd_rowsub_pair_bf16", flat_width))) return rc;
   if ((rc = check_inv_aligned(inv_flat, "inv_flat"))) return rc;
   if ((rc = check_dpre_bound(batch, rows, cout, CFSD_DT_F32, kAbsentRow))) return rc;
-  const int nslab = bf::dw_slabs(batch, rows, cin, cout);  // as cfsd_dw_reduce_batch's fused = 2 items
+  const int nslab = bf::dw_slabs(batch, rows, cin, cout);  // as cfsd_dw_reduce_batch's fused = CFSD_DW_BF16 items
   if ((rc = check_workspace(workspace_bytes, (size_t)nslab * ((size_t)cout * kSeq * cin + cout) * sizeof(float))))
     return rc;
   return bf::launch_bwd_rowsub16_pair((const bf16_t*)x, idx, dpre, inv_flat, flat_width, w, (const bf16_t*)elu_y,
@@ -3392,7 +3392,7 @@ extern "C" int cfsd_spiral_conv_bwd_flat_pair_bf16(const void* x, const int32_t*
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_flat_pair_bf16: 32 -> 32, batch %% 16 == 0 only");
   if ((rc = check_flat_width("spiral_conv_bwd_flat_pair_bf16", flat_width, 20))) return rc;
   if ((rc = check_inv_aligned(inv_flat, "inv_flat"))) return rc;
-  const int nslab = bf::dw_slabs(batch, rows, cin, cout);  // as cfsd_dw_reduce_batch's fused = 2 items
+  const int nslab = bf::dw_slabs(batch, rows, cin, cout);  // as cfsd_dw_reduce_batch's fused = CFSD_DW_BF16 items
   if ((rc = check_workspace(workspace_bytes, (size_t)nslab * ((size_t)cout * kSeq * cin + cout) * sizeof(float))))
     return rc;
   return bf::launch_bwd_vm16_pair((const bf16_t*)x, idx, (const bf16_t*)dpre, inv_flat, flat_width, (const bf16_t*)w,
@@ -3475,7 +3475,7 @@ extern "C" int cfsd_spiral_conv_bwd_x(const void* x, int x_dt, const int32_t* id
 
 // Fused dx + dW of the xyz output conv for vertex-major operands through the
 // flat inverse list (spiral_conv_vm32.hip conv_bwd_out_vm): same workspace
-// and slab layout as cfsd_spiral_conv_bwd_x (deferred items use fused = 1).
+// and slab layout as cfsd_spiral_conv_bwd_x (deferred items use fused = CFSD_DW_FUSED).
 extern "C" int cfsd_spiral_conv_bwd_out_flat(const void* x, int x_dt, const int32_t* idx, const float* dpre,
                                              int dpre_dt, const int32_t* inv_flat, int flat_width, const float* w,
                                              const void* elu_y, void* dx, float* dw, float* db, float* workspace,
@@ -3514,11 +3514,11 @@ static int fill_red_item(const cfsd_dw_slabs& q, int i, Item& d) {
   d.cin = q.cin;
   d.cout = q.cout;
   const int K = kSeq * q.cin;
-  if (q.fused == 2 && mfma_shape(q.cin, q.cout)) {  // bf16 MFMA dW: plain slabs
+  if (q.fused == CFSD_DW_BF16 && mfma_shape(q.cin, q.cout)) {  // bf16 MFMA dW: plain slabs
     d.kind = 1;
     d.n_slabs = bf::dw_slabs(q.batch, q.rows, q.cin, q.cout);
     d.n_el = q.cout * K + q.cout;
-  } else if (q.fused && fused_small(q.cin, q.cout)) {
+  } else if (q.fused != CFSD_DW_PLAIN && fused_small(q.cin, q.cout)) {
     d.kind = 1;
     d.n_slabs = fused_small_gx((long)q.batch * q.vsrc);
     d.n_el = q.cout * K + q.cout;
@@ -3528,7 +3528,7 @@ static int fill_red_item(const cfsd_dw_slabs& q, int i, Item& d) {
     if (g.kind == kDwMfma || g.kind == kDwLat) {
       const int U = (int)dw_units(q.cin, q.cout);
       d.kind = 0;
-      const bool vm = q.fused == 3 && dw_vm32_path(1, 1, q.cin, q.cout, q.batch);  // as dw_f32 chose
+      const bool vm = q.fused == CFSD_DW_VM32 && dw_vm32_path(1, 1, q.cin, q.cout, q.batch);  // as dw_f32 chose
       d.n_slabs = g.kind == kDwLat ? lat_slabs(g.gx)
                   : vm             ? vm32::dw_slabs(q.batch, q.rows, g.gx)
                                    : dw_mfma_slabs(q.cin, q.cout, g.gx);

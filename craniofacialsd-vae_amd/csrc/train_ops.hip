@@ -911,7 +911,7 @@ constexpr int kBnGroups = 8;
 constexpr int kBnSyncA = 0, kBnSyncL = kBnSyncLine, kBnSyncTop = 2 * kBnSyncLine, kBnSyncSub = 3 * kBnSyncLine;
 constexpr int kBnSyncFlag = kBnSyncSub + kBnGroups * kBnSyncLine;  // L-done flag per E group
 constexpr int kBnSyncErr = kBnSyncTop + 1;  // sticky: bit r set when a role-r wait timed out (host-checked)
-static_assert(kBnSyncFlag + kBnGroups * kBnSyncLine == 608, "cfsd.h documents 608 sync ints");
+static_assert(kBnSyncFlag + kBnGroups * kBnSyncLine == CFSD_BN_SYNC_INTS, "cfsd.h: CFSD_BN_SYNC_INTS");
 static_assert(kBnSyncErr == CFSD_BN_SYNC_ERR, "cfsd.h documents the error word");
 constexpr int kBnDwRows = 4;  // encoder dW rows per E workgroup (x loaded once for all of them)
 constexpr int kBnWPer = kLinSplitN * kLinSplitK / 256;  // W-slice floats per thread of an A workgroup

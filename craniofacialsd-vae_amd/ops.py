@@ -13,10 +13,9 @@ from . import _abi
 from ._abi import call, ptr, stream_ptr
 from .topology import INV_HEAD
 
-ACT_NONE = 0
-ACT_ELU = 1
-DT_F32 = 0    # CFSD_DT_F32
-DT_BF16 = 1   # CFSD_DT_BF16
+_H = _abi.CONSTANTS  # the integer CFSD_* #defines of include/cfsd.h, by name
+ACT_NONE, ACT_ELU = _H["CFSD_ACT_NONE"], _H["CFSD_ACT_ELU"]
+DT_F32, DT_BF16 = _H["CFSD_DT_F32"], _H["CFSD_DT_BF16"]
 _DTYPES = {torch.float32: DT_F32, torch.bfloat16: DT_BF16}
 
 
@@ -48,7 +47,7 @@ def _needx(t, shape, name="tensor"):
 
 
 # ------------------------------------------------------------------ layouts
-VM = 0x10  # CFSD_VM: vertex-major storage flag of a *_dt argument (include/cfsd.h)
+VM = _H["CFSD_VM"]  # vertex-major storage flag of a *_dt argument
 
 
 def is_vm(t):
@@ -105,8 +104,13 @@ def _out(out, shape, like, name="out"):
 
 
 # ------------------------------------------------------------------ spiral conv
-CONV_FWD, CONV_BWD_DATA, CONV_BWD_WEIGHT, CONV_BWD_FUSED = 0, 1, 2, 3  # CFSD_CONV_*: roles of spiral_conv_has_shape
-GEN_MAX_SEQ, GEN_MAX_CH = 32, 512                   # CFSD_GEN_MAX_SEQ, CFSD_GEN_MAX_CH
+# roles of spiral_conv_has_shape
+CONV_FWD, CONV_BWD_DATA = _H["CFSD_CONV_FWD"], _H["CFSD_CONV_BWD_DATA"]
+CONV_BWD_WEIGHT, CONV_BWD_FUSED = _H["CFSD_CONV_BWD_WEIGHT"], _H["CFSD_CONV_BWD_FUSED"]
+GEN_MAX_SEQ, GEN_MAX_CH = _H["CFSD_GEN_MAX_SEQ"], _H["CFSD_GEN_MAX_CH"]
+# which launch left a deferred weight gradient's slabs (cfsd_dw_slabs.fused)
+DW_PLAIN, DW_FUSED = _H["CFSD_DW_PLAIN"], _H["CFSD_DW_FUSED"]
+DW_BF16, DW_VM32 = _H["CFSD_DW_BF16"], _H["CFSD_DW_VM32"]
 
 
 def spiral_conv_has_shape(role, seq, cin, cout):
@@ -162,15 +166,56 @@ def _conv_ws(workspace, device, need):
     return workspace, nbytes
 
 
+def _conv_dims(x, idx):
+    """(bsz, vsrc, rows, seq, cin) of x [bsz, vsrc, cin] gathered through idx [rows, seq] (checked)."""
+    bsz, vsrc, cin = x.shape
+    rows, seq = idx.shape
+    _need(idx, (rows, seq), torch.int32, "idx")
+    return bsz, vsrc, rows, seq, cin
+
+
+def _need_dw_db(dw, db, cout, k):
+    """The dw [cout, k] / db [cout] pair: both, or neither (the reduction is deferred)."""
+    if dw is not None or db is not None:
+        _need(dw, (cout, k), name="dw")
+        _need(db, (cout,), name="db")
+
+
+def _need_inv(inv, vsrc, rows, seq):
+    """The (inv_ptr, inv_row, inv_head) triple of ``topology.inverse_spiral``."""
+    inv_ptr, inv_row, inv_head = inv
+    _need(inv_ptr, (vsrc * seq + 1,), torch.int32, "inv_ptr")
+    _need(inv_row, (rows * seq,), torch.int32, "inv_row")
+    _need(inv_head, (vsrc * seq, INV_HEAD), torch.int32, "inv_head")
+    return inv_ptr, inv_row, inv_head
+
+
+def _need_flat(flat, vsrc):
+    """The (table, width) pair of ``topology.inverse_flat``."""
+    table, width = flat
+    _need(table, (vsrc, width), torch.int32, "inv_flat")
+    return table, width
+
+
+def _need_like(ref, ref_name, shape, dtype, **operands):
+    """Optional operands (dx, elu_y) of ``shape`` and ``dtype`` that share ``ref``'s layout."""
+    for name, t in operands.items():
+        if t is not None:
+            _needl(t, shape, name, dtype)
+            _same_layout(ref, t, f"{ref_name} and {name}")
+
+
+def _need_vm(t, shape, name, dtype):
+    if not is_vm(_needl(t, shape, name, dtype)):
+        raise ValueError(f"{name} must be vertex-major")
+
+
 def spiral_conv_fwd(x, idx, w, b, act=ACT_NONE, out=None, workspace=None, general=False):
     """y[b, r] = act(b + W . concat_s x[b, idx[r, s]])  (model.py:27-41).
     A shape without a specialised instance takes the general-shape kernel;
     ``general=True`` forces it (tests, tools/bench_general_conv.py)."""
-    bsz, vsrc, cin = x.shape
-    rows, seq = idx.shape
-    cout = w.shape[0]
+    (bsz, vsrc, rows, seq, cin), cout = _conv_dims(x, idx), w.shape[0]
     _need(x, None, name="x")
-    _need(idx, (rows, seq), torch.int32, "idx")
     _need(w, (cout, seq * cin), name="w")
     if b is not None:
         _need(b, (cout,), name="bias")
@@ -191,16 +236,12 @@ def spiral_conv_bwd_data(dpre, inv, w, vsrc, elu_y=None, out=None, workspace=Non
     (inv_ptr, inv_row, inv_head) triple of ``topology.inverse_spiral``.
     ``general``: as :func:`spiral_conv_fwd`."""
     bsz, rows, cout = dpre.shape
-    inv_ptr, inv_row, inv_head = inv
-    seq = (inv_ptr.numel() - 1) // vsrc
+    seq = (inv[0].numel() - 1) // vsrc
     cin = w.shape[1] // seq
     _need(dpre, None, name="dpre")
-    _need(inv_ptr, (vsrc * seq + 1,), torch.int32, "inv_ptr")
-    _need(inv_row, (rows * seq,), torch.int32, "inv_row")
-    _need(inv_head, (vsrc * seq, INV_HEAD), torch.int32, "inv_head")
+    inv_ptr, inv_row, inv_head = _need_inv(inv, vsrc, rows, seq)
     _need(w, (cout, seq * cin), name="w")
-    if elu_y is not None:
-        _need(elu_y, (bsz, vsrc, cin), name="elu_y")
+    _need_like(dpre, "dpre", (bsz, vsrc, cin), torch.float32, elu_y=elu_y)
     dx = _out(out, (bsz, vsrc, cin), dpre)
     if general or not spiral_conv_has_shape(CONV_BWD_DATA, seq, cin, cout):  # no instance: the general kernel
         _check_gen_limits(seq, cin, cout)
@@ -228,20 +269,12 @@ def spiral_conv_bwd_weight(x, idx, dpre, dw, db, workspace, general=False):
     slabs (:class:`DeferredGenDw`) are reduced by ``spiral_conv_gen_dw_reduce``
     or as an item of ``dw_reduce_batch``, which reduces them in a launch of
     their own before the batched one.  ``general``: as :func:`spiral_conv_fwd`."""
-    bsz, vsrc, cin = x.shape
-    rows, seq = idx.shape
-    cout = dpre.shape[2]
+    (bsz, vsrc, rows, seq, cin), cout = _conv_dims(x, idx), dpre.shape[2]
     _need(x, None, name="x")
-    _need(idx, (rows, seq), torch.int32, "idx")
     _need(dpre, (bsz, rows, cout), name="dpre")
-    if dw is not None or db is not None:
-        _need(dw, (cout, seq * cin), name="dw")
-        _need(db, (cout,), name="db")
-    _need(workspace, None, name="workspace")
-    need = spiral_conv_bwd_weight_workspace(bsz, rows, seq, cin, cout, general)
-    nbytes = workspace.numel() * workspace.element_size()
-    if nbytes < need:
-        raise ValueError(f"workspace {nbytes} < {need} bytes")
+    _need_dw_db(dw, db, cout, seq * cin)
+    workspace, nbytes = _conv_ws(_need(workspace, None, name="workspace"), x.device,
+                                 spiral_conv_bwd_weight_workspace(bsz, rows, seq, cin, cout, general))
     if general or not spiral_conv_has_shape(CONV_BWD_WEIGHT, seq, cin, cout):  # no instance: the general kernel
         _check_gen_limits(seq, cin, cout)
         call("cfsd_spiral_conv_gen_bwd_weight", ptr(x), ptr(idx), ptr(dpre), ptr(dw), ptr(db), ptr(workspace),
@@ -250,7 +283,7 @@ def spiral_conv_bwd_weight(x, idx, dpre, dw, db, workspace, general=False):
     call("cfsd_spiral_conv_bwd_weight", ptr(x), ptr(idx), ptr(dpre), ptr(dw), ptr(db),
          ptr(workspace), ctypes.c_size_t(nbytes), bsz, vsrc, rows, seq, cin, cout, stream_ptr())
     if dw is None:
-        return DeferredDw(workspace, bsz, vsrc, rows, cin, cout, False)
+        return DeferredDw(workspace, bsz, vsrc, rows, cin, cout, DW_PLAIN)
     return None
 
 
@@ -334,36 +367,24 @@ def spiral_conv_bwd_paired(bsz, vsrc, rows, seq, cin, cout):
 def spiral_conv_bwd(x, idx, dpre, inv, w, dw, db, dx=None, elu_y=None, workspace=None):
     """Fused dX (skipped when ``dx`` is None) + dW/db of one SpiralConv; same
     results as spiral_conv_bwd_data followed by spiral_conv_bwd_weight."""
-    bsz, vsrc, cin = x.shape
-    rows, seq = idx.shape
-    cout = dpre.shape[2]
-    inv_ptr, inv_row, inv_head = inv
+    (bsz, vsrc, rows, seq, cin), cout = _conv_dims(x, idx), dpre.shape[2]
     _need(x, None, name="x")
-    _need(idx, (rows, seq), torch.int32, "idx")
     _need(dpre, (bsz, rows, cout), name="dpre")
-    _need(inv_ptr, (vsrc * seq + 1,), torch.int32, "inv_ptr")
-    _need(inv_row, (rows * seq,), torch.int32, "inv_row")
-    _need(inv_head, (vsrc * seq, INV_HEAD), torch.int32, "inv_head")
+    inv_ptr, inv_row, inv_head = _need_inv(inv, vsrc, rows, seq)
     _need(w, (cout, seq * cin), name="w")
-    if dw is not None or db is not None:
-        _need(dw, (cout, seq * cin), name="dw")
-        _need(db, (cout,), name="db")
-    if dx is not None:
-        _need(dx, (bsz, vsrc, cin), name="dx")
-    if elu_y is not None:
-        _need(elu_y, (bsz, vsrc, cin), name="elu_y")
+    _need_dw_db(dw, db, cout, seq * cin)
+    _need_like(x, "x", (bsz, vsrc, cin), torch.float32, dx=dx, elu_y=elu_y)
+    ws, nb = _conv_ws(workspace, x.device, spiral_conv_bwd_workspace(bsz, vsrc, rows, seq, cin, cout))
     if spiral_conv_bwd_is_general(seq, cin, cout, dx=dx is not None):  # the library refuses: two launches
-        ws, _ = _conv_ws(workspace, x.device, spiral_conv_bwd_workspace(bsz, vsrc, rows, seq, cin, cout))
         if dx is not None:
             spiral_conv_bwd_data(dpre, inv, w, vsrc, elu_y=elu_y, out=dx)
         d = spiral_conv_bwd_weight(x, idx, dpre, dw, db, ws)
         return (dx, d) if dw is None else dx
-    ws, nb = _conv_ws(workspace, x.device, spiral_conv_bwd_workspace(bsz, vsrc, rows, seq, cin, cout))
     call("cfsd_spiral_conv_bwd", ptr(x), ptr(idx), ptr(dpre), ptr(inv_ptr), ptr(inv_row),
          ptr(inv_head), ptr(w), ptr(elu_y), ptr(dx), ptr(dw), ptr(db), ptr(ws), ctypes.c_size_t(nb),
          bsz, vsrc, rows, seq, cin, cout, stream_ptr())
     if dw is None:  # deferred weight gradient
-        return dx, DeferredDw(ws, bsz, vsrc, rows, cin, cout, True)
+        return dx, DeferredDw(ws, bsz, vsrc, rows, cin, cout, DW_FUSED)
     return dx
 
 
@@ -376,45 +397,28 @@ def spiral_conv_bwd_rowsub(x, idx, dpre, flat, w, dw, db, dx, elu_y=None, worksp
     """dX + dW/db of a conv evaluated on a row subset (an Enblock conv):
     dG = dpre.W at the kept rows, then the ascending-order gather-sum of dG
     through ``flat`` = ``topology.inverse_flat``'s (table, width)."""
-    bsz, vsrc, cin = x.shape
-    rows, seq = idx.shape
-    cout = dpre.shape[2]
-    table, width = flat
-    if is_vm(x):  # vertex-major fp32 x (the fp32 step's E1): cfsd_spiral_conv_bwd_rowsub_x
-        _needl(x, (bsz, vsrc, cin), "x", torch.float32)
-    else:
-        _need(x, None, name="x")
-    _need(idx, (rows, seq), torch.int32, "idx")
+    (bsz, vsrc, rows, seq, cin), cout = _conv_dims(x, idx), dpre.shape[2]
+    # batch-major x, or vertex-major fp32 x (the fp32 step's E1: cfsd_spiral_conv_bwd_rowsub_x)
+    _needl(x, None, "x", torch.float32)
     _need(dpre, (bsz, rows, cout), name="dpre")
-    _need(table, (vsrc, width), torch.int32, "inv_flat")
+    table, width = _need_flat(flat, vsrc)
     _need(w, (cout, seq * cin), name="w")
-    if dw is not None or db is not None:
-        _need(dw, (cout, seq * cin), name="dw")
-        _need(db, (cout,), name="db")
-    if is_vm(x):  # x, dx and elu_y share the source level's layout
-        _needl(dx, (bsz, vsrc, cin), "dx", torch.float32)
-        _same_layout(x, dx, "x and dx")
-        if elu_y is not None:
-            _needl(elu_y, (bsz, vsrc, cin), "elu_y", torch.float32)
-            _same_layout(x, elu_y, "x and elu_y")
-    else:
-        _need(dx, (bsz, vsrc, cin), name="dx")
-        if elu_y is not None:
-            _need(elu_y, (bsz, vsrc, cin), name="elu_y")
+    _need_dw_db(dw, db, cout, seq * cin)
+    if dx is None:
+        raise ValueError("dx is required")
+    _need_like(x, "x", (bsz, vsrc, cin), torch.float32, dx=dx, elu_y=elu_y)  # the source level's layout
     need = spiral_conv_bwd_rowsub_workspace(bsz, vsrc, rows, seq, cin, cout)
     if need == 0:
         raise ValueError(f"no row-subset backward for {cin} -> {cout} channels")
     ws, nb = _conv_ws(workspace, x.device, need)
+    rest = (ptr(idx), ptr(dpre), ptr(table), width, ptr(w), ptr(elu_y), ptr(dx), ptr(dw), ptr(db), ptr(ws),
+            ctypes.c_size_t(nb), bsz, vsrc, rows, seq, cin, cout, stream_ptr())
     if is_vm(x):
-        call("cfsd_spiral_conv_bwd_rowsub_x", ptr(x), _st(x), ptr(idx), ptr(dpre), ptr(table), width, ptr(w),
-             ptr(elu_y), ptr(dx), ptr(dw), ptr(db), ptr(ws), ctypes.c_size_t(nb), bsz, vsrc, rows, seq,
-             cin, cout, stream_ptr())
+        call("cfsd_spiral_conv_bwd_rowsub_x", ptr(x), _st(x), *rest)
     else:
-        call("cfsd_spiral_conv_bwd_rowsub", ptr(x), ptr(idx), ptr(dpre), ptr(table), width, ptr(w),
-             ptr(elu_y), ptr(dx), ptr(dw), ptr(db), ptr(ws), ctypes.c_size_t(nb), bsz, vsrc, rows, seq,
-             cin, cout, stream_ptr())
+        call("cfsd_spiral_conv_bwd_rowsub", ptr(x), *rest)
     if dw is None:  # deferred weight gradient (slabs at the workspace start)
-        return dx, DeferredDw(ws, bsz, vsrc, rows, cin, cout, True)
+        return dx, DeferredDw(ws, bsz, vsrc, rows, cin, cout, DW_FUSED)
     return dx
 
 
@@ -426,15 +430,12 @@ def spiral_conv_bwd_data_rowsub(dpre, flat, w, vsrc, elu_y=None, out=None, works
     """dx of a row-subset conv (dG = dpre.W at the kept rows, then the
     ascending flat gather); ``out``/``elu_y`` fp32 or bf16 (bf16 path)."""
     bsz, rows, cout = dpre.shape
-    table, width = flat
     cin = w.shape[1] // 9
     _need(dpre, None, name="dpre")
-    _need(table, (vsrc, width), torch.int32, "inv_flat")
+    table, width = _need_flat(flat, vsrc)
     _need(w, (cout, 9 * cin), name="w")
     _needl(out, (bsz, vsrc, cin), "out")
-    if elu_y is not None:
-        _needl(elu_y, (bsz, vsrc, cin), "elu_y", out.dtype)
-        _same_layout(out, elu_y, "out and elu_y")
+    _need_like(out, "out", (bsz, vsrc, cin), out.dtype, elu_y=elu_y)
     need = spiral_conv_bwd_data_rowsub_workspace(bsz, rows, 9, cin)
     if need == 0:
         raise ValueError(f"no row-subset backward for {cin} -> {cout} channels")
@@ -445,10 +446,8 @@ def spiral_conv_bwd_data_rowsub(dpre, flat, w, vsrc, elu_y=None, out=None, works
 
 
 def spiral_gather(x, idx, out=None):
-    bsz, vsrc, cin = x.shape
-    rows, seq = idx.shape
+    bsz, vsrc, rows, seq, cin = _conv_dims(x, idx)
     _need(x, None, name="x")
-    _need(idx, (rows, seq), torch.int32, "idx")
     g = _out(out, (bsz, rows, seq * cin), x)
     call("cfsd_spiral_gather", ptr(x), ptr(idx), ptr(g), bsz, vsrc, rows, seq, cin, stream_ptr())
     return g
@@ -794,8 +793,8 @@ def latent_bwd(mulv, eps, z, dz_dec, dlat, dmulv, latent, train, is_vae, sigmoid
          latent, int(train), int(is_vae), int(sigmoid), stream_ptr())
 
 
-BN_SYNC_INTS = 608  # cfsd_bottleneck_bwd's counters and flags (19 x one 128-B line)
-BN_SYNC_ERR = 65    # CFSD_BN_SYNC_ERR: the sticky timed-out-wait word inside them
+BN_SYNC_INTS = _H["CFSD_BN_SYNC_INTS"]  # cfsd_bottleneck_bwd's counters and flags (19 x one 128-B line)
+BN_SYNC_ERR = _H["CFSD_BN_SYNC_ERR"]    # the sticky timed-out-wait word inside them
 
 
 def bottleneck_exchange_floats(batch, latent, nd, ne):
@@ -979,8 +978,7 @@ def vertex_errors(out, gt, to_mm=89.11, mean=None, std=None, want_l1=False, want
     return (err,) + ((l1,) if want_l1 else ()) + ((mm,) if want_mesh_mean else ())
 
 
-RM_MAX_REGIONS = 64  # CFSD_RM_MAX_REGIONS
-RM_THREADS = 256     # CFSD_RM_THREADS
+RM_MAX_REGIONS, RM_THREADS = _H["CFSD_RM_MAX_REGIONS"], _H["CFSD_RM_THREADS"]
 
 
 def group_vertex_errors(frames, n, to_mm=89.11, mean=None, std=None):
@@ -1046,11 +1044,10 @@ def reconstruction_error_stats(mesh_means):
 
 
 # ------------------------------------------------------------------ classifiers
-CLS_MAX_D = 128      # widest column window of cfsd_class_stats / cfsd_discriminant_scores
-CLS_MAX_CLASSES = 64
-MLP_MAX_LAYERS = 6
-MLP_MAX_WIDTH = 1024
-MLP_MAX_BS = 16
+CLS_MAX_D = _H["CFSD_CLS_MAX_D"]  # widest column window of cfsd_class_stats / cfsd_discriminant_scores
+CLS_MAX_CLASSES = _H["CFSD_CLS_MAX_CLASSES"]
+MLP_MAX_LAYERS, MLP_MAX_WIDTH = _H["CFSD_MLP_MAX_LAYERS"], _H["CFSD_MLP_MAX_WIDTH"]
+MLP_MAX_BS = _H["CFSD_MLP_MAX_BS"]
 
 
 def _window(z, cols, name="z"):
@@ -1242,7 +1239,7 @@ def mlp_head_step(z, batch_idx, label_table, class_weight, params, acc, dims, bs
 
 
 # ------------------------------------------------------------------ latent fitting
-NN_TILE = 16 # CFSD_NN_TILE: reference points per chunk of cfsd_nn_points (include/cfsd.h)
+NN_TILE = _H["CFSD_NN_TILE"]  # reference points per chunk of cfsd_nn_points
 
 
 def _points(t, name):
@@ -1369,9 +1366,8 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_nor
 
 
 # ------------------------------------------------------------------ surface fitting
-PF_GROUP = 16      # CFSD_PF_GROUP: faces per group sphere of cfsd_point_face (include/cfsd.h)
-PF_CULL = 1        # CFSD_PF_CULL
-PF_PREPARED = 2    # CFSD_PF_PREPARED
+PF_GROUP = _H["CFSD_PF_GROUP"]  # faces per group sphere of cfsd_point_face
+PF_CULL, PF_PREPARED = _H["CFSD_PF_CULL"], _H["CFSD_PF_PREPARED"]  # its flags
 PF_WAVE = 64       # queries per workgroup of cfsd_point_face: one row of its stats
 
 
@@ -1627,8 +1623,8 @@ def surface_distance(gen_verts, gen_faces, scan_verts, scan_faces=None, batch_re
 
 
 # ------------------------------------------------------------------ rendering
-RN_GROUP = 16        # CFSD_RN_GROUP: faces per group box of cfsd_rasterize (include/cfsd.h)
-RN_MAX_SIZE = 4096   # CFSD_RN_MAX_SIZE: largest image side
+RN_GROUP = _H["CFSD_RN_GROUP"]        # faces per group box of cfsd_rasterize
+RN_MAX_SIZE = _H["CFSD_RN_MAX_SIZE"]  # largest image side
 
 
 class RenderFaces:
@@ -1814,11 +1810,8 @@ def cast(src, out):
 
 
 def spiral_conv_fwd_x(x, idx, w, w_bf16, b, act, out):
-    bsz, vsrc, cin = x.shape
-    rows, seq = idx.shape
-    cout = w.shape[0]
+    (bsz, vsrc, rows, seq, cin), cout = _conv_dims(x, idx), w.shape[0]
     _needl(x, None, "x")
-    _need(idx, (rows, seq), torch.int32, "idx")
     _need(w, (cout, seq * cin), name="w")
     if w_bf16 is not None:
         _need(w_bf16, (cout, seq * cin), torch.bfloat16, "w_bf16")
@@ -1832,20 +1825,15 @@ def spiral_conv_fwd_x(x, idx, w, w_bf16, b, act, out):
 
 def spiral_conv_bwd_data_x(dpre, inv, w_bf16, vsrc, elu_y=None, out=None):
     bsz, rows, cout = dpre.shape
-    inv_ptr, inv_row, inv_head = inv
-    seq = (inv_ptr.numel() - 1) // vsrc
+    seq = (inv[0].numel() - 1) // vsrc
     cin = w_bf16.shape[1] // seq
     _needl(dpre, None, "dpre")
-    _need(inv_ptr, (vsrc * seq + 1,), torch.int32, "inv_ptr")
-    _need(inv_row, (rows * seq,), torch.int32, "inv_row")
-    _need(inv_head, (vsrc * seq, INV_HEAD), torch.int32, "inv_head")
+    inv_ptr, inv_row, inv_head = _need_inv(inv, vsrc, rows, seq)
     _need(w_bf16, (cout, seq * cin), torch.bfloat16, "w_bf16")
     if out is None:
         out = torch.empty((bsz, vsrc, cin), dtype=torch.bfloat16, device=dpre.device)
     _needl(out, (bsz, vsrc, cin), "dx", torch.bfloat16)
-    if elu_y is not None:
-        _needl(elu_y, (bsz, vsrc, cin), "elu_y", torch.bfloat16)
-        _same_layout(out, elu_y, "dx and elu_y")
+    _need_like(out, "dx", (bsz, vsrc, cin), torch.bfloat16, elu_y=elu_y)
     call("cfsd_spiral_conv_bwd_data_x", ptr(dpre), _st(dpre), ptr(inv_ptr), ptr(inv_row), ptr(inv_head),
          ptr(w_bf16), ptr(elu_y), ptr(out), _st(out), bsz, vsrc, rows, seq, cin, cout, stream_ptr())
     return out
@@ -1857,23 +1845,20 @@ def spiral_conv_bwd_data_flat(dpre, flat, w, vsrc, elu_y=None, out=None):
     shadow; dx / elu_y bf16) or fp32 (dx, elu_y and dpre fp32: the fp32
     step's vertex-major kernel)."""
     bsz, rows, cout = dpre.shape
-    table, width = flat
     seq = 9
     cin = w.shape[1] // seq
     dt = w.dtype
     if dt not in (torch.float32, torch.bfloat16):
         raise ValueError(f"w must be fp32 or bf16, got {dt}")
     _needl(dpre, None, "dpre")
-    _need(table, (vsrc, width), torch.int32, "inv_flat")
+    table, width = _need_flat(flat, vsrc)
     _need(w, (cout, seq * cin), dt, "w")
     if out is None:
         out = vm_empty(bsz, vsrc, cin, dtype=dt, device=dpre.device)
     _needl(out, (bsz, vsrc, cin), "dx", dt)
     if dt == torch.float32 and dpre.dtype != torch.float32:
         raise ValueError("fp32 dx needs fp32 dpre")
-    if elu_y is not None:
-        _needl(elu_y, (bsz, vsrc, cin), "elu_y", dt)
-        _same_layout(out, elu_y, "dx and elu_y")
+    _need_like(out, "dx", (bsz, vsrc, cin), dt, elu_y=elu_y)
     call("cfsd_spiral_conv_bwd_data_flat", ptr(dpre), _st(dpre), ptr(table), width, ptr(w), ptr(elu_y),
          ptr(out), _st(out), bsz, vsrc, rows, seq, cin, cout, stream_ptr())
     return out
@@ -1890,28 +1875,20 @@ def spiral_conv_bwd_weight_x_workspace(bsz, rows, seq, cin, cout, x_dtype=torch.
 def spiral_conv_bwd_weight_x(x, idx, dpre, dw, db, workspace):
     """dW/db of a bf16-path conv (x / dpre fp32 or bf16); ``dw is db is None``
     defers the reduction (returns a DeferredDw for dw_reduce_batch)."""
-    bsz, vsrc, cin = x.shape
-    rows, seq = idx.shape
-    cout = dpre.shape[2]
+    (bsz, vsrc, rows, seq, cin), cout = _conv_dims(x, idx), dpre.shape[2]
     _needl(x, None, "x")
-    _need(idx, (rows, seq), torch.int32, "idx")
     _needl(dpre, (bsz, rows, cout), "dpre")
-    if dw is not None or db is not None:
-        _need(dw, (cout, seq * cin), name="dw")
-        _need(db, (cout,), name="db")
-    _need(workspace, None, name="workspace")
-    need = spiral_conv_bwd_weight_x_workspace(bsz, rows, seq, cin, cout, x.dtype)
-    nbytes = workspace.numel() * workspace.element_size()
-    if nbytes < need:
-        raise ValueError(f"workspace {nbytes} < {need} bytes")
+    _need_dw_db(dw, db, cout, seq * cin)
+    workspace, nbytes = _conv_ws(_need(workspace, None, name="workspace"), x.device,
+                                 spiral_conv_bwd_weight_x_workspace(bsz, rows, seq, cin, cout, x.dtype))
     call("cfsd_spiral_conv_bwd_weight_x", ptr(x), _st(x), ptr(idx), ptr(dpre), _st(dpre), ptr(dw), ptr(db),
          ptr(workspace), ctypes.c_size_t(nbytes), bsz, vsrc, rows, seq, cin, cout, stream_ptr())
-    if dw is None:  # bf16 32/64-channel slabs are plain (kind 2); fp32 x: the fp32 kernels' slabs
+    if dw is None:  # bf16 32/64-channel slabs are plain (DW_BF16); fp32 x: the fp32 kernels' slabs
         mfma = cin in (32, 64) and cout in (32, 64) and x.dtype == torch.bfloat16
-        # fp32 32 -> 32 with vertex-major x and dpre: conv_dw_vm32's slabs (3)
+        # fp32 32 -> 32 with vertex-major x and dpre: conv_dw_vm32's slabs (DW_VM32)
         vm32 = (x.dtype == torch.float32 and is_vm(x) and is_vm(dpre) and cin == 32 and cout == 32
                 and bsz % 16 == 0)
-        return DeferredDw(workspace, bsz, vsrc, rows, cin, cout, 2 if mfma else (3 if vm32 else 0))
+        return DeferredDw(workspace, bsz, vsrc, rows, cin, cout, DW_BF16 if mfma else (DW_VM32 if vm32 else DW_PLAIN))
     return None
 
 
@@ -1925,23 +1902,14 @@ def spiral_conv_bwd_flat_pair(x, idx, dpre, flat, w, dw, db, dx, elu_y=None, wor
     launch (``cfsd_spiral_conv_bwd_flat_pair``, ABI 4.10): the flat-list dx
     of :func:`spiral_conv_bwd_data_flat` and coarse-geometry dW slabs.
     ``dw is db is None`` defers the reduction (returns a DeferredDw)."""
-    bsz, vsrc, cin = x.shape
-    rows, seq = idx.shape
-    cout = dpre.shape[2]
-    table, width = flat
-    for t, nm, shp in ((x, "x", (bsz, vsrc, cin)), (dpre, "dpre", (bsz, rows, cout)), (dx, "dx", (bsz, vsrc, cin))):
-        _needl(t, shp, nm, torch.float32)
-        if not is_vm(t):
-            raise ValueError(f"spiral_conv_bwd_flat_pair: {nm} must be vertex-major")
-    if elu_y is not None:
-        _needl(elu_y, (bsz, vsrc, cin), "elu_y", torch.float32)
-        _same_layout(dx, elu_y, "dx and elu_y")
-    _need(idx, (rows, seq), torch.int32, "idx")
-    _need(table, (vsrc, width), torch.int32, "inv_flat")
+    (bsz, vsrc, rows, seq, cin), cout = _conv_dims(x, idx), dpre.shape[2]
+    _need_vm(x, (bsz, vsrc, cin), "x", torch.float32)
+    _need_vm(dpre, (bsz, rows, cout), "dpre", torch.float32)
+    _need_vm(dx, (bsz, vsrc, cin), "dx", torch.float32)
+    _need_like(dx, "dx", (bsz, vsrc, cin), torch.float32, elu_y=elu_y)
+    table, width = _need_flat(flat, vsrc)
     _need(w, (cout, seq * cin), torch.float32, "w")
-    if dw is not None or db is not None:
-        _need(dw, (cout, seq * cin), name="dw")
-        _need(db, (cout,), name="db")
+    _need_dw_db(dw, db, cout, seq * cin)
     need = spiral_conv_bwd_flat_pair_workspace(bsz, rows, seq, cin, cout)
     if need == 0:
         raise ValueError(f"no vertex-major pair for {cin} -> {cout} channels")
@@ -1949,7 +1917,7 @@ def spiral_conv_bwd_flat_pair(x, idx, dpre, flat, w, dw, db, dx, elu_y=None, wor
     call("cfsd_spiral_conv_bwd_flat_pair", ptr(x), ptr(idx), ptr(dpre), ptr(table), width, ptr(w), ptr(elu_y),
          ptr(dx), ptr(dw), ptr(db), ptr(ws), ctypes.c_size_t(nb), bsz, vsrc, rows, seq, cin, cout, stream_ptr())
     if dw is None:
-        return DeferredDw(ws, bsz, vsrc, rows, cin, cout, 3)
+        return DeferredDw(ws, bsz, vsrc, rows, cin, cout, DW_VM32)
     return None
 
 
@@ -1959,26 +1927,19 @@ def spiral_conv_bwd_flat_pair_bf16(x, idx, dpre, flat, w16, dx, elu_y=None, work
     deferred (``cfsd_spiral_conv_bwd_flat_pair_bf16``, ABI 4.11): the dx of
     :func:`spiral_conv_bwd_data_flat` and the slabs of
     :func:`spiral_conv_bwd_weight_x` in one launch; returns the DeferredDw."""
-    bsz, vsrc, cin = x.shape
-    rows, seq = idx.shape
-    cout = dpre.shape[2]
-    table, width = flat
-    for t, nm, shp in ((x, "x", (bsz, vsrc, cin)), (dpre, "dpre", (bsz, rows, cout)), (dx, "dx", (bsz, vsrc, cin))):
-        _needl(t, shp, nm, torch.bfloat16)
-        if not is_vm(t):
-            raise ValueError(f"spiral_conv_bwd_flat_pair_bf16: {nm} must be vertex-major")
-    if elu_y is not None:
-        _needl(elu_y, (bsz, vsrc, cin), "elu_y", torch.bfloat16)
-        _same_layout(dx, elu_y, "dx and elu_y")
-    _need(idx, (rows, seq), torch.int32, "idx")
-    _need(table, (vsrc, width), torch.int32, "inv_flat")
+    (bsz, vsrc, rows, seq, cin), cout = _conv_dims(x, idx), dpre.shape[2]
+    _need_vm(x, (bsz, vsrc, cin), "x", torch.bfloat16)
+    _need_vm(dpre, (bsz, rows, cout), "dpre", torch.bfloat16)
+    _need_vm(dx, (bsz, vsrc, cin), "dx", torch.bfloat16)
+    _need_like(dx, "dx", (bsz, vsrc, cin), torch.bfloat16, elu_y=elu_y)
+    table, width = _need_flat(flat, vsrc)
     _need(w16, (cout, seq * cin), torch.bfloat16, "w16")
-    _need(workspace, None, name="workspace")
-    nbytes = workspace.numel() * workspace.element_size()
+    workspace, nbytes = _conv_ws(_need(workspace, None, name="workspace"), x.device,
+                                 spiral_conv_bwd_weight_x_workspace(bsz, rows, seq, cin, cout))
     call("cfsd_spiral_conv_bwd_flat_pair_bf16", ptr(x), ptr(idx), ptr(dpre), ptr(table), width, ptr(w16),
          ptr(elu_y), ptr(dx), ptr(workspace), ctypes.c_size_t(nbytes), bsz, vsrc, rows, seq, cin, cout,
          stream_ptr())
-    return DeferredDw(workspace, bsz, vsrc, rows, cin, cout, 2)
+    return DeferredDw(workspace, bsz, vsrc, rows, cin, cout, DW_BF16)
 
 
 def spiral_conv_bwd_rowsub_pair_bf16(x, idx, dpre, flat, w, dx, elu_y=None, workspace=None):
@@ -1988,59 +1949,40 @@ def spiral_conv_bwd_rowsub_pair_bf16(x, idx, dpre, flat, w, dx, elu_y=None, work
     rows, fp32 ``w``; bf16 vertex-major ``dx`` / ``elu_y``) and the deferred
     slabs of :func:`spiral_conv_bwd_weight_x` (bf16 vertex-major ``x``);
     returns the DeferredDw."""
-    bsz, vsrc, cin = x.shape
-    rows, seq = idx.shape
-    cout = dpre.shape[2]
-    table, width = flat
-    for t, nm in ((x, "x"), (dx, "dx")):
-        _needl(t, (bsz, vsrc, cin), nm, torch.bfloat16)
-        if not is_vm(t):
-            raise ValueError(f"spiral_conv_bwd_rowsub_pair_bf16: {nm} must be vertex-major")
-    if elu_y is not None:
-        _needl(elu_y, (bsz, vsrc, cin), "elu_y", torch.bfloat16)
-        _same_layout(dx, elu_y, "dx and elu_y")
+    (bsz, vsrc, rows, seq, cin), cout = _conv_dims(x, idx), dpre.shape[2]
+    _need_vm(x, (bsz, vsrc, cin), "x", torch.bfloat16)
+    _need_vm(dx, (bsz, vsrc, cin), "dx", torch.bfloat16)
+    _need_like(dx, "dx", (bsz, vsrc, cin), torch.bfloat16, elu_y=elu_y)
     _need(dpre, (bsz, rows, cout), torch.float32, "dpre")
-    _need(idx, (rows, seq), torch.int32, "idx")
-    _need(table, (vsrc, width), torch.int32, "inv_flat")
+    table, width = _need_flat(flat, vsrc)
     _need(w, (cout, seq * cin), torch.float32, "w")
-    _need(workspace, None, name="workspace")
-    nbytes = workspace.numel() * workspace.element_size()
+    workspace, nbytes = _conv_ws(_need(workspace, None, name="workspace"), x.device,
+                                 spiral_conv_bwd_weight_x_workspace(bsz, rows, seq, cin, cout))
     call("cfsd_spiral_conv_bwd_rowsub_pair_bf16", ptr(x), ptr(idx), ptr(dpre), ptr(table), width, ptr(w),
          ptr(elu_y), ptr(dx), ptr(workspace), ctypes.c_size_t(nbytes), bsz, vsrc, rows, seq, cin, cout,
          stream_ptr())
-    return DeferredDw(workspace, bsz, vsrc, rows, cin, cout, 2)
+    return DeferredDw(workspace, bsz, vsrc, rows, cin, cout, DW_BF16)
 
 
 def spiral_conv_bwd_x(x, idx, dpre, inv, w, dw, db, dx=None, elu_y=None, workspace=None):
     """Fused dx + dW of the xyz output conv with bf16 (or fp32) x / elu_y /
     dx in either layout."""
-    bsz, vsrc, cin = x.shape
-    rows, seq = idx.shape
-    cout = dpre.shape[2]
-    inv_ptr, inv_row, inv_head = inv
+    (bsz, vsrc, rows, seq, cin), cout = _conv_dims(x, idx), dpre.shape[2]
     xdt = x.dtype
     if xdt not in (torch.float32, torch.bfloat16):
         raise ValueError(f"x must be fp32 or bf16, got {xdt}")
     _needl(x, None, "x", xdt)
-    _need(idx, (rows, seq), torch.int32, "idx")
     _needl(dpre, (bsz, rows, cout), "dpre", torch.float32)
-    _need(inv_head, (vsrc * seq, INV_HEAD), torch.int32, "inv_head")
+    inv_ptr, inv_row, inv_head = _need_inv(inv, vsrc, rows, seq)
     _need(w, (cout, seq * cin), name="w")
-    if dx is not None:
-        _needl(dx, (bsz, vsrc, cin), "dx", xdt)
-        _same_layout(x, dx, "x and dx")
-    if elu_y is not None:
-        _needl(elu_y, (bsz, vsrc, cin), "elu_y", xdt)
-        _same_layout(x, elu_y, "x and elu_y")
-    if dw is not None or db is not None:
-        _need(dw, (cout, seq * cin), name="dw")
-        _need(db, (cout,), name="db")
+    _need_like(x, "x", (bsz, vsrc, cin), xdt, dx=dx, elu_y=elu_y)
+    _need_dw_db(dw, db, cout, seq * cin)
     ws, nb = _conv_ws(workspace, x.device, spiral_conv_bwd_workspace(bsz, vsrc, rows, seq, cin, cout))
     call("cfsd_spiral_conv_bwd_x", ptr(x), _st(x), ptr(idx), ptr(dpre), _st(dpre), ptr(inv_ptr), ptr(inv_row),
          ptr(inv_head), ptr(w), ptr(elu_y), ptr(dx), ptr(dw), ptr(db), ptr(ws), ctypes.c_size_t(nb),
          bsz, vsrc, rows, seq, cin, cout, stream_ptr())
     if dw is None:
-        return dx, DeferredDw(ws, bsz, vsrc, rows, cin, cout, 1)
+        return dx, DeferredDw(ws, bsz, vsrc, rows, cin, cout, DW_FUSED)
     return dx
 
 
@@ -2048,31 +1990,20 @@ def spiral_conv_bwd_out_flat(x, idx, dpre, flat, w, dw, db, dx=None, elu_y=None,
     """Fused dx + dW of the xyz output conv (32 -> 3) with vertex-major x /
     elu_y / dx (fp32 or bf16) and dpre, through the flat inverse list
     (``topology.spiral_flat``); batch a multiple of 16."""
-    bsz, vsrc, cin = x.shape
-    rows, seq = idx.shape
-    cout = dpre.shape[2]
-    table, width = flat
+    (bsz, vsrc, rows, seq, cin), cout = _conv_dims(x, idx), dpre.shape[2]
     xdt = x.dtype
-    if not (is_vm(x) and is_vm(dpre)):
-        raise ValueError("x and dpre must be vertex-major")
-    _needl(x, None, "x", xdt)
-    _need(idx, (rows, seq), torch.int32, "idx")
-    _needl(dpre, (bsz, rows, cout), "dpre", torch.float32)
-    _need(table, (vsrc, width), torch.int32, "inv_flat")
+    _need_vm(x, None, "x", xdt)
+    _need_vm(dpre, (bsz, rows, cout), "dpre", torch.float32)
+    table, width = _need_flat(flat, vsrc)
     _need(w, (cout, seq * cin), name="w")
-    for t, nm in ((dx, "dx"), (elu_y, "elu_y")):
-        if t is not None:
-            _needl(t, (bsz, vsrc, cin), nm, xdt)
-            _same_layout(x, t, f"x and {nm}")
-    if dw is not None or db is not None:
-        _need(dw, (cout, seq * cin), name="dw")
-        _need(db, (cout,), name="db")
+    _need_like(x, "x", (bsz, vsrc, cin), xdt, dx=dx, elu_y=elu_y)
+    _need_dw_db(dw, db, cout, seq * cin)
     ws, nb = _conv_ws(workspace, x.device, spiral_conv_bwd_workspace(bsz, vsrc, rows, seq, cin, cout))
     call("cfsd_spiral_conv_bwd_out_flat", ptr(x), _st(x), ptr(idx), ptr(dpre), _st(dpre), ptr(table), width,
          ptr(w), ptr(elu_y), ptr(dx), ptr(dw), ptr(db), ptr(ws), ctypes.c_size_t(nb), bsz, vsrc, rows, seq, cin,
          cout, stream_ptr())
     if dw is None:
-        return dx, DeferredDw(ws, bsz, vsrc, rows, cin, cout, 1)
+        return dx, DeferredDw(ws, bsz, vsrc, rows, cin, cout, DW_FUSED)
     return dx
 
 

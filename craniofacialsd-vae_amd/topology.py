@@ -24,6 +24,8 @@ tables the kernels read:
 import numpy as np
 import torch
 
+from ._abi import CONSTANTS as _H
+
 
 def _i32(a):
     a = np.asarray(a)
@@ -49,7 +51,7 @@ def csr_transpose_from_coo(row, col, val, n):
     return csr_from_coo(col, row, val, n)
 
 
-INV_HEAD = 4  # list entries kept inline per (u, s) key (CFSD_INV_HEAD)
+INV_HEAD = _H["CFSD_INV_HEAD"]  # list entries kept inline per (u, s) key
 
 
 def inverse_spiral(idx, vsrc):

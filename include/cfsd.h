@@ -105,13 +105,16 @@ size_t cfsd_spiral_conv_bwd_weight_workspace(int batch, int rows, int seq, int c
 /* Deferred weight gradients.  cfsd_spiral_conv_bwd_weight / cfsd_spiral_conv_bwd
  * called with dw == db == NULL leave their per-workgroup partial sums in
  * `workspace` and skip the reduction; cfsd_dw_reduce_batch then reduces up
- * to 16 such layers (each with its own workspace) in ONE launch, with the
- * same fixed summation order (identical results).  `fused` = 1: the partials
- * came from cfsd_spiral_conv_bwd(_x) on a small-output layer (cout*seq <= 32);
- * 2: from cfsd_spiral_conv_bwd_weight_x on a 32/64-channel layer (bf16); 3: from
- * cfsd_spiral_conv_bwd_weight_x on a 32 -> 32 fp32 layer with vertex-major x
- * and dpre, batch % 16 == 0 (ABI 4.3), or from cfsd_spiral_conv_bwd_flat_pair
- * (ABI 4.10). */
+ * to CFSD_DW_REDUCE_MAX such layers (each with its own workspace) in ONE
+ * launch, with the same fixed summation order (identical results).  `fused`
+ * is one of the CFSD_DW_* codes: which launch left the partials. */
+#define CFSD_DW_REDUCE_MAX 16
+#define CFSD_DW_PLAIN 0 /* cfsd_spiral_conv_bwd_weight; _bwd_weight_x on fp32 x or the xyz input layer */
+#define CFSD_DW_FUSED 1 /* a dx + dW call: cfsd_spiral_conv_bwd(_x) (small-output layers, cout*seq <= 32:
+                           their own slabs), _bwd_out_flat, _bwd_rowsub(_x) */
+#define CFSD_DW_BF16 2  /* cfsd_spiral_conv_bwd_weight_x on a 32/64-channel bf16 layer; the *_pair_bf16 calls */
+#define CFSD_DW_VM32 3  /* cfsd_spiral_conv_bwd_weight_x on a 32 -> 32 fp32 layer with vertex-major x and
+                           dpre, batch % 16 == 0 (ABI 4.3); cfsd_spiral_conv_bwd_flat_pair (ABI 4.10) */
 typedef struct {
   const float* workspace;
   float* dw;
@@ -161,7 +164,7 @@ int cfsd_spiral_conv_bwd_paired(int batch, int vsrc, int rows, int seq, int cin,
  * inv_flat [vsrc][flat_width] int32, -1 padded, 16-B aligned rows,
  * flat_width in {4, 8, 12, 16} (>= the largest fan-in).  dw/db exactly as
  * cfsd_spiral_conv_bwd_weight (dw == db == NULL defers: cfsd_dw_reduce_batch
- * item with fused = 1).  cin = 32, cout in {32, 64}.
+ * item with fused = CFSD_DW_FUSED).  cin = 32, cout in {32, 64}.
  * workspace: cfsd_spiral_conv_bwd_rowsub_workspace() bytes (0 = unsupported). */
 size_t cfsd_spiral_conv_bwd_rowsub_workspace(int batch, int vsrc, int rows, int seq, int cin,
                                              int cout);
@@ -189,7 +192,7 @@ int cfsd_spiral_conv_fwd_in_swap(const float* data, const int32_t* batch_idx, co
  * flat inverse list, elu_y may be NULL) and the weight-gradient slabs of
  * cfsd_spiral_conv_bwd_weight_x as interleaved workgroups, two per CU.
  * Bit-identical to those two calls.  dw == db == NULL defers
- * (cfsd_dw_reduce_batch item with fused = 3).  inv_flat as
+ * (cfsd_dw_reduce_batch item with fused = CFSD_DW_VM32).  inv_flat as
  * cfsd_spiral_conv_bwd_data_flat (flat_width in {8, 12, 16, 20}).
  * workspace: cfsd_spiral_conv_bwd_flat_pair_workspace() bytes (0 = unsupported). */
 size_t cfsd_spiral_conv_bwd_flat_pair_workspace(int batch, int rows, int seq, int cin, int cout);
@@ -202,7 +205,7 @@ int cfsd_spiral_conv_bwd_flat_pair(const float* x, const int32_t* idx, const flo
  * fp32 w, fp32 products; dx / elu_y bf16 vertex-major, rounded once) and the
  * weight-gradient slabs of cfsd_spiral_conv_bwd_weight_x (x bf16
  * vertex-major) as two workgroup roles of ONE launch; always deferred
- * (cfsd_dw_reduce_batch item with fused = 2).  32 -> 32, batch % 16 == 0,
+ * (cfsd_dw_reduce_batch item with fused = CFSD_DW_BF16).  32 -> 32, batch % 16 == 0,
  * flat_width in {4, 8, 12, 16}.  Same values as the two calls. */
 int cfsd_spiral_conv_bwd_rowsub_pair_bf16(const void* x, const int32_t* idx, const float* dpre,
                                           const int32_t* inv_flat, int flat_width, const float* w, const void* elu_y,
@@ -210,7 +213,7 @@ int cfsd_spiral_conv_bwd_rowsub_pair_bf16(const void* x, const int32_t* idx, con
                                           int rows, int seq, int cin, int cout, void* stream);
 /* The same pair on the bf16 step's tensors (ABI 4.11): x, dpre, dx, elu_y
  * bf16 vertex-major, w the bf16 weight shadow; always deferred
- * (cfsd_dw_reduce_batch item with fused = 2; workspace as
+ * (cfsd_dw_reduce_batch item with fused = CFSD_DW_BF16; workspace as
  * cfsd_spiral_conv_bwd_weight_x_workspace).  Same values as
  * cfsd_spiral_conv_bwd_data_flat + cfsd_spiral_conv_bwd_weight_x. */
 int cfsd_spiral_conv_bwd_flat_pair_bf16(const void* x, const int32_t* idx, const void* dpre, const int32_t* inv_flat,
@@ -422,7 +425,7 @@ int cfsd_linear_bwd_split(const float* x, const float* w, const float* dy, float
  * on workgroups of lower index) and read the values they wait for from
  * `exchange` (cfsd_bottleneck_bwd_exchange_floats(batch, latent, nd, ne)
  * device floats, contents unspecified: each 128-B line is written by ONE
- * workgroup); `sync` is 608 device int32 (19 counters and flags, one 128-B
+ * workgroup); `sync` is CFSD_BN_SYNC_INTS device int32 (19 counters and flags, one 128-B
  * line each) that must be zero before the first call and are left zero by
  * every call -- except sync[CFSD_BN_SYNC_ERR], a sticky word a wait that
  * timed out sets (the values are then wrong: the caller must check it and
@@ -430,6 +433,7 @@ int cfsd_linear_bwd_split(const float* x, const float* w, const float* dy, float
  * latent_bwd_parts + linear_bwd, except that dh itself is never stored.
  * batch <= 16, latent <= 128, cup a multiple of 64, nd <= 5120, ne =
  * (is_vae ? 2 : 1) x latent <= 160. */
+#define CFSD_BN_SYNC_INTS 608
 #define CFSD_BN_SYNC_ERR 65
 size_t cfsd_bottleneck_bwd_exchange_floats(int batch, int latent, int nd, int ne);
 int cfsd_bottleneck_bwd(const int32_t* up_ptr, const int32_t* up_col, const float* up_val, const float* g,
@@ -611,8 +615,8 @@ int cfsd_spiral_conv_bwd_data_flat(const void* dpre, int dpre_dt, const int32_t*
 /* dW/db (fp32): 32/64-channel layers (x bf16, dpre bf16/fp32; or x and dpre
  * fp32, each batch-major or vertex-major) and the xyz input layer (x fp32,
  * dpre bf16 or fp32).  dw == db == NULL defers the reduction
- * (cfsd_dw_reduce_batch item with fused = 2 for the bf16 32/64-channel kind,
- * 0 for fp32 x and for the input layer). */
+ * (cfsd_dw_reduce_batch item with fused = CFSD_DW_BF16 for the bf16 32/64-channel kind,
+ * CFSD_DW_PLAIN for fp32 x and for the input layer). */
 size_t cfsd_spiral_conv_bwd_weight_x_workspace(int batch, int rows, int seq, int cin, int cout);
 int cfsd_spiral_conv_bwd_weight_x(const void* x, int x_dt, const int32_t* idx, const void* dpre,
                                   int dpre_dt, float* dw, float* db, float* workspace,
@@ -620,7 +624,7 @@ int cfsd_spiral_conv_bwd_weight_x(const void* x, int x_dt, const int32_t* idx, c
                                   int cin, int cout, void* stream);
 /* Fused dx + dW of the xyz output layer (cout*seq <= 32) with x, elu_y, dx
  * bf16 (or all three fp32, ABI 4.1) and dpre fp32 (workspace:
- * cfsd_spiral_conv_bwd_workspace; deferred items use fused = 1).  x_dt's
+ * cfsd_spiral_conv_bwd_workspace; deferred items use fused = CFSD_DW_FUSED).  x_dt's
  * storage type and CFSD_VM flag are those of x, elu_y and dx; dpre_dt =
  * CFSD_DT_F32 [| CFSD_VM]. */
 int cfsd_spiral_conv_bwd_x(const void* x, int x_dt, const int32_t* idx, const float* dpre,
@@ -633,7 +637,7 @@ int cfsd_spiral_conv_bwd_x(const void* x, int x_dt, const int32_t* idx, const fl
  * per source vertex the spiral transpose is one walk of its flat inverse
  * list (topology.inverse_flat, width 8/12/16/20), dx = W^T-products of the
  * folded 3-wide dpre, dW = folded dpre (x) x.  Same workspace, slab layout
- * and deferred kind (fused = 1) as cfsd_spiral_conv_bwd_x. */
+ * and deferred kind (fused = CFSD_DW_FUSED) as cfsd_spiral_conv_bwd_x. */
 int cfsd_spiral_conv_bwd_out_flat(const void* x, int x_dt, const int32_t* idx, const float* dpre,
                                   int dpre_dt, const int32_t* inv_flat, int flat_width, const float* w,
                                   const void* elu_y, void* dx, float* dw, float* db, float* workspace,
@@ -864,7 +868,7 @@ int cfsd_interpolate_colors(const int32_t* pix_to_face, const float* bary, const
  * [0, n_classes) contributes to nothing.  Two passes in fp32 (mean first):
  *   count [C] int32, mean [C, d] (0 for an empty class),
  *   scatter [C, d, d] = sum_{i: label_i = c} (z_i - mean_c)(z_i - mean_c)^T.
- * d <= 128, n_classes <= 64.  workspace: cfsd_class_stats_workspace() bytes
+ * d <= CFSD_CLS_MAX_D, n_classes <= CFSD_CLS_MAX_CLASSES.  workspace: cfsd_class_stats_workspace() bytes
  * (per-slice partial sums, merged in ascending slice order).
  *
  * cfsd_discriminant_scores: z as above; mean [C, d]; whiten [Cw, d, d] with
@@ -875,7 +879,7 @@ int cfsd_interpolate_colors(const int32_t* pix_to_face, const float* bary, const
  * (each output may be NULL).
  *
  * cfsd_mlp_fwd: the whole MLPClassifier in one launch over n rows of
- * z [n, dims[0]]: n_layers <= 6 Linear layers, every width <= 1024, `dims`
+ * z [n, dims[0]]: n_layers <= CFSD_MLP_MAX_LAYERS Linear layers, every width <= CFSD_MLP_MAX_WIDTH, `dims`
  * a HOST array of n_layers + 1 widths, a ReLU after EVERY layer, the last
  * included (model.py:196-197), so logits >= 0.  params: one flat fp32 buffer
  * in state_dict order, W_0 [dims[1], dims[0]], b_0, W_1, ...
@@ -884,7 +888,7 @@ int cfsd_interpolate_colors(const int32_t* pix_to_face, const float* bary, const
  *
  * cfsd_mlp_train_steps: n_steps consecutive steps of mlp_classifier_epoch
  * (model_manager.py:428-446) over the rows [row0 + t bs, row0 + (t + 1) bs) of
- * z [n_rows, dims[0]] / label [n_rows], bs <= 16; two launches per step:
+ * z [n_rows, dims[0]] / label [n_rows], bs <= CFSD_MLP_MAX_BS; two launches per step:
  *  1. one workgroup: forward; loss = sum_i w[y_i] (logsumexp(o_i) - o_i[y_i]) /
  *     sum_i w[y_i] (CrossEntropyLoss(class_weight)), acc = 100 correct / bs;
  *     acc[3] += {loss, acc, 1}; *step += 1; the activation gradients (ReLU' = 0
@@ -896,6 +900,11 @@ int cfsd_interpolate_colors(const int32_t* pix_to_face, const float* bary, const
  * train == 0: launch 1 without gradients (the validation epoch); params, m,
  * v, step untouched (m, v, step, workspace may be NULL).  Labels are clamped
  * into range.  workspace: cfsd_mlp_workspace(dims, n_layers, bs) bytes. */
+#define CFSD_CLS_MAX_D 128
+#define CFSD_CLS_MAX_CLASSES 64
+#define CFSD_MLP_MAX_LAYERS 6
+#define CFSD_MLP_MAX_WIDTH 1024
+#define CFSD_MLP_MAX_BS 16
 size_t cfsd_class_stats_workspace(int n, int d, int n_classes);
 int cfsd_class_stats(const float* z, const int32_t* label, int32_t* count, float* mean, float* scatter,
                      void* workspace, size_t workspace_bytes, int n, int ld, int col0, int d,
@@ -914,7 +923,7 @@ int cfsd_mlp_train_steps(const float* z, const int32_t* label, const float* clas
 
 /* cfsd_mlp_head_step (ABI 4.18): the MLP classifier as a head of the VAE step
  * (classifier.mlp_training_type: end2end, model_manager.py:295-318): one step
- * of cfsd_mlp_train_steps' two launches on bs <= 16 rows of the step's latent
+ * of cfsd_mlp_train_steps' two launches on bs <= CFSD_MLP_MAX_BS rows of the step's latent
  * codes, whose loss gradient also flows back into the latent.
  *   z: row i < bs at z + i * row_stride * ld_z (dims[0] floats).  row_stride =
  *     bs + 1 takes the diagonal of a swapped bs x bs group

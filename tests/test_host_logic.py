@@ -288,3 +288,115 @@ def test_engine_requires_laplacian(topo_npz):
     topo = topology.DeviceTopology.from_npz(npz, device="cpu")
     with pytest.raises(ValueError, match="Laplacian"):
         E.SDVAEEngine(topo, E.ModelSpec(), device="cpu")
+
+
+# ---------------------------------------------------------------- the ABI read from cfsd.h
+_REFUSED = {
+    "double parameter": ("int cfsd_a(const float* x, double scale);", "cfsd_a"),
+    "struct by value": ("typedef struct { int n; } cfsd_s;\nint cfsd_b(cfsd_s s, int n);", "cfsd_b"),
+    "function pointer": ("int cfsd_c(void (*done)(int), int n);", "cfsd_c"),
+    "variadic": ("int cfsd_d(const char* fmt, ...);", "cfsd_d"),
+    "long parameter": ("int cfsd_e(long n);", "cfsd_e"),
+    "array parameter": ("int cfsd_f(int dims[4]);", "cfsd_f"),
+    "pointer return": ("float* cfsd_g(int n);", "cfsd_g"),
+    # the attribute splits the prototype: the pattern misses it, the occurrence count sees it
+    "split prototype": ("int cfsd_ok(int n);\nint cfsd_h(int n)\n    __attribute__((warn_unused_result));", "cfsd_h"),
+    "float define": ("#define CFSD_X 1.5\nint cfsd_ok(int n);", "CFSD_X"),
+    "expression define": ("#define CFSD_Y (CFSD_Z + 1)\n", "CFSD_Y"),
+    "pointer among several fields": ("typedef struct { float *a, b; } cfsd_t;", "cfsd_t"),
+}
+
+
+@pytest.mark.parametrize("defect", sorted(_REFUSED))
+def test_header_parser_refuses_rather_than_guesses(defect):
+    text, named = _REFUSED[defect]
+    with pytest.raises(_abi.CfsdError, match=named):
+        _abi.parse_header(text)
+
+
+def test_header_parser_reads_the_forms_the_header_uses():
+    sigs, structs, consts = _abi.parse_header("""
+/* a comment naming cfsd_nothing(int) and #define CFSD_NOT 3 */
+#ifndef CFSD_H
+#define CFSD_H
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define CFSD_N (-2)
+#define CFSD_FLAG 0x10 /* trailing comment */
+#define CFSD_TEN 10
+#define CFSD_TYPE(dt) ((dt) & 0xf)
+const char* cfsd_a(void);
+typedef struct {
+  const float* workspace;
+  float* dw;
+  int batch, rows, fused;
+} cfsd_slabs;
+size_t cfsd_b(const cfsd_slabs* items, uint16_t* shadow,
+              size_t n, unsigned long long seed,
+              float lr, const int32_t* step, int k, void* stream);
+#ifdef __cplusplus
+}
+#endif
+#endif
+""")
+    P, I, F, Z, U = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_ulonglong
+    assert sigs == {"cfsd_a": (ctypes.c_char_p, []), "cfsd_b": (Z, [P, P, Z, U, F, P, I, P])}
+    assert structs == {"cfsd_slabs": [("workspace", P), ("dw", P), ("batch", I), ("rows", I), ("fused", I)]}
+    assert consts == {"CFSD_N": -2, "CFSD_FLAG": 16, "CFSD_TEN": 10}
+
+
+def test_dw_slabs_layout():
+    """cfsd_dw_slabs as the compiler lays it out: three pointers, six ints."""
+    assert ctypes.sizeof(_abi.DwSlabs) == 48
+    names = ["workspace", "dw", "db", "batch", "vsrc", "rows", "cin", "cout", "fused"]
+    assert [n for n, _ in _abi.DwSlabs._fields_] == names
+    assert [getattr(_abi.DwSlabs, n).offset for n in names] == [0, 8, 16, 24, 28, 32, 36, 40, 44]
+    assert len(_abi.SIGNATURES) == len(header_functions())
+
+
+_HEADER_CONSTANTS = {
+    "ops": ["ACT_NONE", "ACT_ELU", "DT_F32", "DT_BF16", "VM", "CONV_FWD", "CONV_BWD_DATA", "CONV_BWD_WEIGHT",
+            "CONV_BWD_FUSED", "GEN_MAX_SEQ", "GEN_MAX_CH", "DW_PLAIN", "DW_FUSED", "DW_BF16", "DW_VM32",
+            "BN_SYNC_INTS", "BN_SYNC_ERR", "RM_MAX_REGIONS", "RM_THREADS", "NN_TILE", "PF_GROUP", "PF_CULL",
+            "PF_PREPARED", "RN_GROUP", "RN_MAX_SIZE", "CLS_MAX_D", "CLS_MAX_CLASSES", "MLP_MAX_LAYERS",
+            "MLP_MAX_WIDTH", "MLP_MAX_BS"],
+    "topology": ["INV_HEAD"],
+}
+
+
+@pytest.mark.parametrize("module,name", [(m, n) for m, ns in _HEADER_CONSTANTS.items() for n in ns])
+def test_python_constants_are_the_headers(module, name):
+    """The value comes from the header's own text, read here with a pattern
+    of this test's (not through the parser under test)."""
+    import importlib
+    src = open(os.path.join(ROOT, "include", "cfsd.h")).read()
+    m = re.search(rf"^#define CFSD_{name} \(?(-?(?:0x[0-9a-fA-F]+|\d+))\)?[ \t]*(?:/\*.*)?$", src, re.M)
+    assert m, f"cfsd.h has no integer #define CFSD_{name}"
+    mod = importlib.import_module("craniofacialsd_vae_amd." + module)
+    assert getattr(mod, name) == int(m.group(1), 0) == _abi.CONSTANTS["CFSD_" + name]
+
+
+def test_limits_and_fused_codes_keep_their_values():
+    """The limits and slab codes that got a name in cfsd.h are the numbers the kernels were built with."""
+    want = {"CLS_MAX_D": 128, "CLS_MAX_CLASSES": 64, "MLP_MAX_LAYERS": 6, "MLP_MAX_WIDTH": 1024, "MLP_MAX_BS": 16,
+            "BN_SYNC_INTS": 608, "DW_REDUCE_MAX": 16, "DW_PLAIN": 0, "DW_FUSED": 1, "DW_BF16": 2, "DW_VM32": 3}
+    assert {k: _abi.CONSTANTS["CFSD_" + k] for k in want} == want
+
+
+@pytest.mark.parametrize("header,named", [
+    (None, "no_such_dir"),                                            # no header at that path
+    ("int cfsd_version(void);\n", "cfsd_dw_slabs"),                   # a header without the struct
+    ("typedef struct { struct { int a; } in; } cfsd_dw_slabs;\n", "cfsd_dw_slabs"),  # a nested brace
+])
+def test_unreadable_header_is_a_cfsd_error(tmp_path, monkeypatch, header, named):
+    """Importing the binding over a header it cannot use raises CfsdError naming the path or the struct."""
+    import importlib.util
+    path = tmp_path / "no_such_dir" / "cfsd.h" if header is None else tmp_path / "cfsd.h"
+    if header is not None:
+        path.write_text(header)
+    monkeypatch.setenv("CFSD_HEADER_PATH", str(path))
+    spec = importlib.util.spec_from_file_location("abi_probe", _abi.__file__)
+    with pytest.raises(RuntimeError, match=named) as e:
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
+    assert type(e.value).__name__ == "CfsdError"
