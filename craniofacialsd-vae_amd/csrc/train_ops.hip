@@ -1620,6 +1620,8 @@ extern "C" int cfsd_latent_bwd(const float* mulv, const float* eps, const float*
                                int latent, int train, int is_vae, int sigmoid, void* stream) {
   if (!mulv || !dz_dec || !dlat || !dmulv) return set_error(CFSD_EINVAL, "latent_bwd: null pointer");
   if (is_vae && train && !eps) return set_error(CFSD_EINVAL, "latent_bwd: eps required");
+  if (!is_vae && sigmoid && !z) return set_error(CFSD_EINVAL, "latent_bwd: z required (sigmoid)");
+  if (batch <= 0 || latent <= 0) return set_error(CFSD_EINVAL, "latent_bwd: bad sizes");
   const int n = batch * latent, nb = (n + 255) / 256;
   hipLaunchKernelGGL(latent_bwd_k, dim3(nb), dim3(256), 0, (hipStream_t)stream, mulv, eps, dz_dec, dlat, dmulv,
                      batch, latent, train, is_vae, sigmoid, z, 1, nb);
@@ -1633,6 +1635,8 @@ extern "C" int cfsd_latent_bwd_parts(const float* mulv, const float* eps, const 
   if (!mulv || !dz_parts || !dlat || !dmulv) return set_error(CFSD_EINVAL, "latent_bwd_parts: null pointer");
   if (n_parts <= 0) return set_error(CFSD_EINVAL, "latent_bwd_parts: n_parts %d", n_parts);
   if (is_vae && train && !eps) return set_error(CFSD_EINVAL, "latent_bwd_parts: eps required");
+  if (!is_vae && sigmoid && !z) return set_error(CFSD_EINVAL, "latent_bwd_parts: z required (sigmoid)");
+  if (batch <= 0 || latent <= 0) return set_error(CFSD_EINVAL, "latent_bwd_parts: bad sizes");
   const int n = batch * latent, nb = (n + 255) / 256;
   hipLaunchKernelGGL(latent_bwd_k, dim3(nb), dim3(256), 0, (hipStream_t)stream, mulv, eps, dz_parts,
                      dlat, dmulv, batch, latent, train, is_vae, sigmoid, z, n_parts, nb);

@@ -725,6 +725,8 @@ def recon_lap_bwd_finalize(pred, gt, unit, lapT_csr, dpred, w_rec, w_lap, partia
     bsz, nv, c = pred.shape
     lay = _loss_layout(pred, gt, unit, dpred)
     _need(lapT_csr[0], (nv + 1,), torch.int32, "lt_ptr")
+    _need(partials, (2 * recon_lap_blocks(bsz, nv),), name="partials")
+    _need(terms, (2,), name="terms")
     _need(out, (5,), name="out")
     if acc is not None:
         _need(acc, (6,), name="acc")
@@ -780,14 +782,23 @@ def latent_linear_fwd(mulv, eps, key, z, dlat, terms, latent, region_size, train
 def latent_bwd(mulv, eps, z, dz_dec, dlat, dmulv, latent, train, is_vae, sigmoid):
     """``dz_dec`` [B, latent], or [parts, B, latent] partial products (summed
     in part order: cfsd_latent_bwd_parts)."""
+    if dz_dec is None or dz_dec.dim() not in (2, 3):
+        raise ValueError("dz_dec must be [B, latent] or [parts, B, latent]")
+    bsz = dz_dec.shape[-2]
+    _need(mulv, (bsz, 2 * latent if is_vae else latent), name="mulv")
     _need(dmulv, tuple(mulv.shape), name="dmulv")
+    _need(dlat, (bsz, 3 * latent), name="dlat")
+    if eps is not None:
+        _need(eps, (bsz, latent), name="eps")
+    # z is required by the sigmoid AE alone (zval * (1 - zval)); when given it is checked in every mode
+    if z is not None or (sigmoid and not is_vae):
+        _need(z, (bsz, latent), name="z")
     if dz_dec.dim() == 3:
-        parts, bsz = dz_dec.shape[:2]
+        parts = dz_dec.shape[0]
         _need(dz_dec, (parts, bsz, latent), name="dz_parts")
         call("cfsd_latent_bwd_parts", ptr(mulv), ptr(eps), ptr(z), ptr(dz_dec), parts, ptr(dlat),
              ptr(dmulv), bsz, latent, int(train), int(is_vae), int(sigmoid), stream_ptr())
         return
-    bsz = dz_dec.shape[0]
     _need(dz_dec, (bsz, latent), name="dz_dec")
     call("cfsd_latent_bwd", ptr(mulv), ptr(eps), ptr(z), ptr(dz_dec), ptr(dlat), ptr(dmulv), bsz,
          latent, int(train), int(is_vae), int(sigmoid), stream_ptr())
@@ -875,6 +886,8 @@ def linear_bwd_split(x, w, dy, dx_parts, dw, db):
 
 
 def loss_finalize(partials, terms, out, acc, bsz, nv, c, w_kl, w_lc, w_lap):
+    _need(partials, (2 * recon_lap_blocks(bsz, nv),), name="partials")
+    _need(terms, (2,), name="terms")
     _need(out, (5,), name="out")
     if acc is not None:
         _need(acc, (6,), name="acc")

@@ -512,7 +512,8 @@ int cfsd_latent_linear_fwd(const float* mulv, const float* eps, const int32_t* k
                            float eta2, const float* w, const float* bias, float* y, int n,
                            void* stream);
 /* Latent head, backward: dmulv (same layout as mulv) from dz_dec (gradient of
- * the decoder input) + dlat.  z is only read for the sigmoid AE variant. */
+ * the decoder input) + dlat.  z is only read for the sigmoid AE variant
+ * (is_vae == 0, sigmoid != 0), where a NULL z is CFSD_EINVAL. */
 int cfsd_latent_bwd(const float* mulv, const float* eps, const float* z, const float* dz_dec,
                     const float* dlat, float* dmulv, int batch, int latent, int train, int is_vae,
                     int sigmoid, void* stream);

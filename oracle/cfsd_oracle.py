@@ -114,9 +114,10 @@ def _w(P, name, low):
     return _q(P[name]) if low else P[name]
 
 
-def encode(P, x, topo, is_vae=True, lp=()):
+def encode(P, x, topo, is_vae=True, lp=(), pre_z_sigmoid=False):
     """``Model.encode`` (``model.py:146-160``): 4x (conv -> ELU -> Pool down),
     vertex-major flatten, Linear mu = en_layers[-1], logvar = en_layers[-2].
+    ``pre_z_sigmoid`` (plain AE only, ``model.py:155-159``): mu = sigmoid(mu).
     ``lp``: levels stored in bf16 (emulates the engine's bf16 precision: those
     activations rounded to bf16, 32/64-channel convs reading them use bf16
     weights); empty = the reference's fp32."""
@@ -133,6 +134,8 @@ def encode(P, x, topo, is_vae=True, lp=()):
     flat = h.reshape(-1, P[f"en_layers.{last}.weight"].shape[1])
     mu = F.linear(flat, P[f"en_layers.{last}.weight"], P[f"en_layers.{last}.bias"])
     logvar = F.linear(flat, P[f"en_layers.{n}.weight"], P[f"en_layers.{n}.bias"]) if is_vae else None
+    if pre_z_sigmoid and not is_vae:
+        mu = torch.sigmoid(mu)
     return mu, logvar
 
 
@@ -158,11 +161,12 @@ def decode(P, z, topo, c_last=None, lp=()):
                        P[f"de_layers.{n + 1}.layer.bias"])
 
 
-def forward(P, x, topo, eps=None, train=True, is_vae=True, lp=()):
+def forward(P, x, topo, eps=None, train=True, is_vae=True, lp=(), pre_z_sigmoid=False):
     """``Model.forward`` + ``_reparameterize`` (``model.py:175-188``), with
     the noise ``eps`` injected instead of ``torch.randn_like``.  AE
-    (``is_vae=False``, kl_weight 0 at ``model_manager.py:67``): z = mu."""
-    mu, logvar = encode(P, x, topo, is_vae, lp)
+    (``is_vae=False``, kl_weight 0 at ``model_manager.py:67``): z = mu
+    (= sigmoid of the Linear's output with ``pre_z_sigmoid``)."""
+    mu, logvar = encode(P, x, topo, is_vae, lp, pre_z_sigmoid)
     if train and is_vae:
         z = mu + eps * torch.exp(0.5 * logvar)
     else:
@@ -258,19 +262,21 @@ def latent_regions(n_regions, latent=75):
     return [(i * rs, (i + 1) * rs) for i in range(n_regions)]
 
 
-def losses(P, x16, topo, key_index, eps, bs=4, w=LOSS_W, is_vae=True, train=True, lp=()):
+def losses(P, x16, topo, key_index, eps, bs=4, w=LOSS_W, is_vae=True, train=True, lp=(), pre_z_sigmoid=False,
+           eta1=0.5, eta2=0.5):
     """Forward + the four losses of ``_do_iteration``
     (``model_manager.py:281-312``); KL only when ``w_kl > 0`` (``:285-288``),
     latent consistency only with swapped batches (``:290-293``).
     ``train=False``: the validation pass (eval mode, z = mu); ``lp``: bf16
-    storage emulation (see :func:`encode`)."""
-    rec, z, mu, lv = forward(P, x16, topo, eps=eps, train=train, is_vae=is_vae, lp=lp)
+    storage emulation (see :func:`encode`); ``eta1`` / ``eta2``: the latent-consistency margins
+    (``optimization.latent_consistency_eta1`` / ``_eta2``, ``model_manager.py:362-363``)."""
+    rec, z, mu, lv = forward(P, x16, topo, eps=eps, train=train, is_vae=is_vae, lp=lp, pre_z_sigmoid=pre_z_sigmoid)
     l_rec = mse_loss(rec, x16)
     l_lap = laplacian_loss(rec, topo.lap)
     l_kl = kl_loss(mu, lv) if w["kl"] > 0 else torch.tensor(0.0)
     if w["lc"] and key_index is not None:
         region = latent_regions(len(topo.region_keys), z.shape[1])[key_index]
-        l_lc = latent_consistency(z, region, bs)
+        l_lc = latent_consistency(z, region, bs, eta1, eta2)
     else:
         l_lc = torch.tensor(0.0)
     tot = l_rec + w["kl"] * l_kl + w["lc"] * l_lc + w["lap"] * l_lap
@@ -301,7 +307,8 @@ class Adam:
             p.addcdiv_(self.m[k], denom, value=-self.lr / bc1)
 
 
-def train_step(P, opt, x4, topo, key_index, eps, w=LOSS_W, is_vae=True, swap=True):
+def train_step(P, opt, x4, topo, key_index, eps, w=LOSS_W, is_vae=True, swap=True, pre_z_sigmoid=False,
+               eta1=0.5, eta2=0.5):
     """One ``_do_iteration(train=True)``: swap -> forward -> losses ->
     backward -> Adam.  ``P`` holds leaf tensors (requires_grad).  ``swap``
     False: a ``swap_features: False`` configuration (no SwapFeatures in the
@@ -314,7 +321,7 @@ def train_step(P, opt, x4, topo, key_index, eps, w=LOSS_W, is_vae=True, swap=Tru
     for p in P.values():
         p.grad = None
     out = losses(P, x16, topo, key_index, None if eps is None else torch.as_tensor(eps),
-                 bs=len(x4), w=w, is_vae=is_vae)
+                 bs=len(x4), w=w, is_vae=is_vae, pre_z_sigmoid=pre_z_sigmoid, eta1=eta1, eta2=eta2)
     out["tot"].backward()
     grads = {k: p.grad.detach().clone() for k, p in P.items()}
     opt.step(P, grads)

@@ -64,6 +64,38 @@ def test_c4_oracle_step_cpu(c4):
     assert x16.shape == (16, 6890, 3)
 
 
+def test_oracle_pre_z_sigmoid_and_margins_cpu():
+    """``pre_z_sigmoid`` (``model.py:155-159``) on the small torus: the plain AE's z is the
+    sigmoid of its encoder Linear, the VAE ignores the flag, and ``losses`` hands eta1 / eta2
+    to the latent consistency (margins 0.3 / 0.01: this model's swapped latents lie so close
+    together that larger ones leave every hinge term active, and then only their sum shows)."""
+    T = O.Topology(ST.torus_topology(nu=32, nv=16, factors=(4, 4)))
+    x = torch.from_numpy(ST.torus_meshes(4, nu=32, nv=16, seed=2))
+    x16 = torch.from_numpy(O.swap_features(x.numpy(), T.region_features, 3))
+    ae = O.make_params(recipe.golden_weights(recipe.param_shapes(num_vert=32, out_ch=[8, 20], latent=22,
+                                                                 is_vae=False), seed=4))
+    with torch.no_grad():
+        mu_linear, _ = O.encode(ae, x16, T, is_vae=False)
+        mu, logvar = O.encode(ae, x16, T, is_vae=False, pre_z_sigmoid=True)
+        out = O.losses(ae, x16, T, 3, None, w=W_BODY, is_vae=False, pre_z_sigmoid=True, eta1=0.3, eta2=0.01)
+        swapped = O.losses(ae, x16, T, 3, None, w=W_BODY, is_vae=False, pre_z_sigmoid=True, eta1=0.01, eta2=0.3)
+    z = out["z"]
+    assert logvar is None and torch.equal(mu, torch.sigmoid(mu_linear)) and torch.equal(z, mu)
+    assert 0 < z.min() and z.max() < 1 and not torch.equal(z, mu_linear)
+    region = O.latent_regions(len(T.region_keys), 22)[3]
+    assert out["lc"] == O.latent_consistency(z, region, 4, 0.3, 0.01)
+    assert abs(out["lc"].item() - swapped["lc"].item()) > 1e-5  # (1.5e-4; rounding is ~1e-8)
+    vae = O.make_params(recipe.golden_weights(recipe.param_shapes(num_vert=32, out_ch=[8, 20], latent=22), seed=4))
+    with torch.no_grad():
+        a = O.encode(vae, x16, T, pre_z_sigmoid=True)
+        b = O.encode(vae, x16, T)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    P = O.make_params({k: v.detach().numpy() for k, v in ae.items()})
+    res, grads, _ = O.train_step(P, O.Adam(P), x.numpy(), T, 3, None, w=W_BODY, is_vae=False, pre_z_sigmoid=True,
+                                 eta1=0.3, eta2=0.8)
+    assert torch.allclose(res["z"], z, rtol=0, atol=1e-6) and all(torch.isfinite(g).all() for g in grads.values())
+
+
 # ----------------------------------------------------------------- GPU
 def _engine(c4):
     from craniofacialsd_vae_amd import engine as E
