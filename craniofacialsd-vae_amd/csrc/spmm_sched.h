@@ -24,6 +24,9 @@ __device__ __forceinline__ void spmm_fold_prefetch(int beg, int end, const int* 
                                                    const float* __restrict__ val,
                                                    const TX* __restrict__ xb, long rs, f32x4& acc) {
 #pragma clang fp contract(off)
+  // an empty row has no entry to clamp to: end - 1 lies before the row, before
+  // col / val themselves when beg == 0 (acc stays 0, the caller stores it)
+  if (beg >= end) return;
   int cc[CK];
   float vv[CK];
 #pragma unroll
@@ -68,6 +71,7 @@ __device__ __forceinline__ void spmm_fold_prefetch8(int beg, int end, const int*
                                                     const bf16_t* __restrict__ xb, long rs, f32x4& acc0,
                                                     f32x4& acc1) {
 #pragma clang fp contract(off)
+  if (beg >= end) return;  // empty row: no col / val access (see spmm_fold_prefetch)
   int cc[CK];
   float vv[CK];
 #pragma unroll

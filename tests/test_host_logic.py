@@ -400,3 +400,69 @@ def test_unreadable_header_is_a_cfsd_error(tmp_path, monkeypatch, header, named)
     with pytest.raises(RuntimeError, match=named) as e:
         spec.loader.exec_module(importlib.util.module_from_spec(spec))
     assert type(e.value).__name__ == "CfsdError"
+
+
+# ------------------------------------------------------------------ SpMM schedule builders
+def _ptr(lens):
+    return np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+
+
+def test_row_schedule():
+    lens = np.array([0, 3, 17, 1, 3, 0, 17, 40, 3, 1])
+    order = topology.row_schedule(_ptr(lens))
+    assert order.dtype == np.int32
+    assert sorted(order.tolist()) == list(range(len(lens)))          # a permutation of the rows
+    assert np.all(np.diff(lens[order]) <= 0)                         # lengths non-increasing
+    assert order.tolist() == [7, 2, 6, 1, 4, 8, 3, 9, 0, 5]           # stable among equal lengths
+    assert topology.row_schedule(_ptr([3, 16, 0, 16])) is None       # longest row exactly 16
+    assert topology.row_schedule(_ptr([3, 17, 0, 16])).tolist() == [1, 3, 0, 2]
+    assert topology.row_schedule(_ptr([])) is None                   # no rows
+    assert topology.row_schedule(_ptr([0, 0])) is None
+    assert topology.row_schedule(_ptr([2, 3]), min_max_len=2).tolist() == [1, 0]
+
+
+def test_scheduled_csr():
+    rs = np.random.RandomState(7)
+    lens = np.array([0, 3, 17, 1, 0, 0, 5, 17, 2, 0])
+    m, n, nnz = len(lens), 11, int(lens.sum())
+    ptr, col, val = _ptr(lens), rs.randint(0, n, nnz).astype(np.int32), rs.standard_normal(nnz).astype(np.float32)
+    order = topology.row_schedule(ptr)
+    for visit in (order, np.arange(m), rs.permutation(m)):
+        ptr_s, col_s, val_s, rows_s = topology.scheduled_csr(ptr, col, val, visit)
+        assert (ptr_s.dtype, col_s.dtype, val_s.dtype, rows_s.dtype) == (np.int32, np.int32, np.float32, np.int32)
+        assert rows_s.tolist() == list(visit)
+        assert ptr_s.tolist() == [0] + np.cumsum(lens[visit]).tolist()  # cumulative visited lengths
+        for i, r in enumerate(visit):                                 # each slot: that row's entries, in order
+            assert col_s[ptr_s[i]:ptr_s[i + 1]].tolist() == col[ptr[r]:ptr[r + 1]].tolist()
+            assert val_s[ptr_s[i]:ptr_s[i + 1]].tobytes() == val[ptr[r]:ptr[r + 1]].tobytes()
+            if lens[r] == 0:
+                assert ptr_s[i] == ptr_s[i + 1]                       # an empty row is an empty slot
+        # scattering the slot results back by rows_s reproduces the plain CSR product
+        x = rs.standard_normal((n, 4)).astype(np.float32)
+        plain = np.stack([sum((x[col[e]] * val[e] for e in range(ptr[r], ptr[r + 1])), np.zeros(4, np.float32))
+                          for r in range(m)])
+        back = np.full((m, 4), np.nan, np.float32)
+        for i in range(m):
+            back[rows_s[i]] = sum((x[col_s[e]] * val_s[e] for e in range(ptr_s[i], ptr_s[i + 1])),
+                                  np.zeros(4, np.float32))
+        assert back.tobytes() == plain.tobytes()
+    nat = topology.scheduled_csr(ptr, col, val, np.arange(m))      # natural order: the input CSR itself
+    assert nat[0].tolist() == ptr.tolist() and nat[1].tolist() == col.tolist()
+    assert nat[2].tobytes() == val.tobytes() and nat[3].tolist() == list(range(m))
+    empty = topology.scheduled_csr(_ptr([0, 0]), col[:0], val[:0], [1, 0])
+    assert empty[0].tolist() == [0, 0, 0] and empty[1].size == 0 and empty[2].size == 0
+    none = topology.scheduled_csr(_ptr([]), col[:0], val[:0], [])
+    assert none[0].tolist() == [0] and none[1].size == 0 and none[3].size == 0
+
+
+def test_uniform_rows():
+    for k in (1, 2, 3, 4):
+        assert topology.uniform_rows(_ptr([k] * 6)) == k
+        assert topology.uniform_rows(_ptr([k])) == k
+    assert topology.uniform_rows(_ptr([0] * 6)) == 0               # k = 0
+    assert topology.uniform_rows(_ptr([5] * 6)) == 0               # k = 5 > max_k
+    assert topology.uniform_rows(_ptr([5] * 6), max_k=5) == 5
+    assert topology.uniform_rows(_ptr([3, 3, 2, 3])) == 0          # mixed lengths
+    assert topology.uniform_rows(_ptr([2, 3, 3, 3])) == 0
+    assert topology.uniform_rows(_ptr([3, 3, 3, 4])) == 0
+    assert topology.uniform_rows(_ptr([])) == 0                    # no rows
