@@ -2614,8 +2614,7 @@ namespace {
 enum DwKind { kDwMfma, kDwLat, kDwInMfma, kDwInSmall, kDwOutSmall, kDwNone };
 struct DwGeom {
   DwKind kind;
-  int gx;  // workgroups (= slabs), or row chunks for kDwLat
-  size_t ws_floats;
+  int gx;  // workgroups, or row chunks for kDwLat
   int rchunk;
 };
 
@@ -2642,7 +2641,7 @@ constexpr int kDwLatWaves = 2048;
 // dispatched only as dx ones retired (stamps: starts up to 11.4 us, span
 // 17.9 us); sized to fit, every workgroup of the launch starts at once.
 DwGeom lat_geom(int batch, int rows, int cin, int cout) {
-  DwGeom g{kDwLat, 0, 0, 0};
+  DwGeom g{kDwLat, 0, 0};
   const long M = (long)batch * rows;
   const long U = (long)dw_units(cin, cout);
   long R = (M * U / kDwLatWaves + 15) / 16 * 16;
@@ -2655,11 +2654,10 @@ DwGeom lat_geom(int batch, int rows, int cin, int cout) {
   }
   g.rchunk = (int)R;
   g.gx = (int)((M + R - 1) / R);
-  g.ws_floats = (size_t)g.gx * U * 1024 + (size_t)g.gx * cout;
   return g;
 }
 DwGeom dw_geom(int batch, int rows, int cin, int cout) {
-  DwGeom g{kDwNone, 0, 0, 0};
+  DwGeom g{kDwNone, 0, 0};
   const long M = (long)batch * rows;
   if ((cin == 32 || cin == 64) && (cout == 32 || cout == 64) && M < kLatDwMax) {
     g = lat_geom(batch, rows, cin, cout);  // few rows
@@ -2671,59 +2669,95 @@ constexpr int kDwTpb = 4;
 constexpr int kDwMaxWg = 512;  // (768: same time, 1.5x the slab traffic)
     if (gx > kDwMaxWg) gx = kDwMaxWg;  // 2 blocks of 9 waves per CU
     g.gx = (int)(gx > 0 ? gx : 1);
-    g.ws_floats = (size_t)g.gx * dw_units(cin, cout) * 1024 + (size_t)g.gx * cout;
   } else if (cin <= 3 && (cout == 32 || cout == 64)) {
     g.kind = kDwInMfma;
     long gx = ((M + 63) / 64 + 3) / 4;  // one 64-row tile per wave per pass
     g.gx = (int)(gx > 512 ? 512 : (gx < 1 ? 1 : gx));
-    g.ws_floats = (size_t)g.gx * ((size_t)cout * kSeq * cin + cout);
   } else if (cin <= 4 && (cout == 16 || cout == 32 || cout == 64)) {
     g.kind = kDwInSmall;
     const long per_blk = 4 * (64 / cout);
     long gx = (M + per_blk * 8 - 1) / (per_blk * 8);  // >= 8 rows per row slot
     g.gx = (int)(gx > 512 ? 512 : (gx < 1 ? 1 : gx));
-    g.ws_floats = (size_t)g.gx * ((size_t)cout * kSeq * cin + cout);
   } else if (cout <= 4 && (cin == 16 || cin == 32 || cin == 64)) {
     g.kind = kDwOutSmall;
     const long per_blk = 4 * (64 / (cin / 4));
     long gx = (M + per_blk * 8 - 1) / (per_blk * 8);
     g.gx = (int)(gx > 512 ? 512 : (gx < 1 ? 1 : gx));
-    g.ws_floats = (size_t)g.gx * ((size_t)cout * kSeq * cin + cout);
   }
   return g;
+}
+// small-output layers (the xyz output conv): dx and the dW slabs from one
+// pass in source-row space (conv_bwd_out_mfma, vm32::conv_bwd_out_vm)
+bool fused_small(int cin, int cout) { return cout * kSeq <= 32 && (cin == 32 || cin == 64); }
+int fused_small_gx(long m_src) {  // ~2 32-row tiles per wave
+  long gx = ((m_src + 31) / 32 + 7) / 8;
+  constexpr int bpc = 0;  // workgroups per CU (0: the occupancy bound)
+  const long cap = bpc > 0 ? (long)bpc * device_cus() : 1024;
+  return (int)(gx > cap ? cap : (gx < 1 ? 1 : gx));
+}
+
+constexpr int kDwVm32 = 1;  // 32 -> 32 with vertex-major x and dpre: vm32::conv_dw_vm32
+bool vm32_shape(int batch, int cin, int cout) { return kDwVm32 && cin == 32 && cout == 32 && batch % 16 == 0; }
+
+// ---- the slabs a weight-gradient launch leaves in its workspace: per-workgroup
+// partial sums of dw and db, summed in slab order by the immediate reduce or by
+// cfsd_dw_reduce_batch.  slab_set() is the one derivation of their layout: every
+// producer, workspace query and reduce takes it from there.
+struct SlabSet {
+  bool unit;      // 1024-float unit slabs with the db partials behind them; else plain [cout x 9 cin | cout] slabs
+  int n_slabs;    // 0: no weight-gradient kernel for these channels
+  int n_el;       // floats of dw and db together (either kind)
+  size_t db_off;  // unit slabs: floats from the workspace start to the db partials
+  size_t floats;  // floats of the workspace the set occupies
+};
+// `code`: the CFSD_DW_* code (cfsd.h) of the launch that leaves the slabs.
+// vsrc is read for the small-output layers' own slabs only (code != PLAIN).
+SlabSet slab_set(int code, int batch, int vsrc, int rows, int cin, int cout) {
+  SlabSet s{false, 0, 0, 0, 0};
+  const DwGeom g = dw_geom(batch, rows, cin, cout);
+  if (code == CFSD_DW_BF16 && mfma_shape(cin, cout)) {
+    s.n_slabs = bf::dw_slabs(batch, rows, cin, cout);
+  } else if (code != CFSD_DW_PLAIN && fused_small(cin, cout)) {
+    s.n_slabs = fused_small_gx((long)batch * vsrc);
+  } else if (g.kind == kDwLat || g.kind == kDwMfma) {
+    s.unit = true;
+    const bool vm32 = code == CFSD_DW_VM32 && vm32_shape(batch, cin, cout);
+    s.n_slabs = g.kind == kDwLat ? lat_slabs(g.gx)  // groups of row chunks
+                : vm32           ? vm32::dw_slabs(batch, rows, g.gx)
+                                 : dw_mfma_slabs(cin, cout, g.gx);
+    s.db_off = (size_t)g.gx * dw_units(cin, cout) * 1024;  // room for one slab per workgroup / row chunk
+  } else if (g.kind != kDwNone) {
+    s.n_slabs = g.gx;
+  }
+  if (s.n_slabs == 0) return s;
+  s.n_el = cout * kSeq * cin + cout;  // (= dw_units * 1024 + cout for the unit kinds)
+  s.floats = s.unit ? s.db_off + (size_t)g.gx * cout : (size_t)s.n_slabs * s.n_el;
+  return s;
 }
 }  // namespace
 
 extern "C" size_t cfsd_spiral_conv_bwd_weight_workspace(int batch, int rows, int seq, int cin,
                                                         int cout) {
   if (batch <= 0 || rows <= 0 || seq != kSeq || cin <= 0 || cout <= 0) return 0;
-  return dw_geom(batch, rows, cin, cout).ws_floats * sizeof(float);
+  return slab_set(CFSD_DW_PLAIN, batch, 0, rows, cin, cout).floats * sizeof(float);
 }
 
-// ---- reduce epilogues: the slabs a weight-gradient launch left in the
-// workspace, summed into dw / db
-// MFMA-shaped layers: 1024-float unit slabs, db partials behind them
-static int reduce_dw_units(bool deferred, int cin, int cout, float* workspace, float* ws_db, float* dw, float* db,
-                           int n_slabs, hipStream_t st) {
+// ---- the immediate reduce: a slab set summed into dw / db
+static int reduce_slab_set(bool deferred, const SlabSet& s, int cin, int cout, float* workspace, float* dw, float* db,
+                           hipStream_t st) {
   if (deferred) return CFSD_OK;  // cfsd_dw_reduce_batch sums the slabs later
-  const int n_el = cout * kSeq * cin + cout;
-  const int rc = for_shape(MfmaShapes{}, cin, cout, [&](auto s) {
-    using S = decltype(s);
-    hipLaunchKernelGGL((conv_dw_reduce<S::cin, S::cout>), dim3((unsigned)((n_el + 63) / 64)), dim3(1024), 0, st,
-                       workspace, ws_db, dw, db, n_slabs);
+  const dim3 grid((unsigned)((s.n_el + 63) / 64));
+  if (!s.unit) {
+    hipLaunchKernelGGL(slab_reduce, grid, dim3(1024), 0, st, workspace, s.n_slabs, s.n_el, dw, cout * kSeq * cin, db);
+    return launch_status("spiral_conv_slab_reduce");
+  }
+  const int rc = for_shape(MfmaShapes{}, cin, cout, [&](auto sh) {
+    using S = decltype(sh);
+    hipLaunchKernelGGL((conv_dw_reduce<S::cin, S::cout>), grid, dim3(1024), 0, st, workspace, workspace + s.db_off, dw,
+                       db, s.n_slabs);
     return launch_status("spiral_conv_bwd_weight_reduce");
   });
   return rc != kNoShape ? rc : set_error(CFSD_EINVAL, "dw reduce: unsupported channels %d -> %d", cin, cout);
-}
-
-// every other layer: n_slabs plain slabs of [cout x 9 cin | cout] floats
-static int reduce_slabs(bool deferred, int cin, int cout, float* workspace, int n_slabs, float* dw, float* db,
-                        hipStream_t st) {
-  if (deferred) return CFSD_OK;
-  const int n_el = cout * kSeq * cin + cout;
-  hipLaunchKernelGGL(slab_reduce, dim3((unsigned)((n_el + 63) / 64)), dim3(1024), 0, st, workspace, n_slabs, n_el, dw,
-                     cout * kSeq * cin, db);
-  return launch_status("spiral_conv_slab_reduce");
 }
 
 template <int CIN, int COUT>
@@ -2768,14 +2802,11 @@ static int dw_xyz_in(const float* x, int xvm, const int* idx, const void* dpre, 
   });
 }
 
-constexpr int kDwVm32 = 1;  // 32 -> 32 with vertex-major x and dpre: vm32::conv_dw_vm32
-// The fp32 weight gradient takes vm32::conv_dw_vm32 (its slabs: cfsd_dw_slabs.fused == CFSD_DW_VM32)
-static bool dw_vm32_path(int xvm, int dpvm, int cin, int cout, int batch) {
-  return kDwVm32 && xvm && dpvm && cin == 32 && cout == 32 && batch % 16 == 0;
-}
 // dW / db of an fp32 conv, x and dpre each batch-major or vertex-major
-// (xvm / dpvm; the small-channel kernels are batch-major only).
-static int dw_f32(const float* x, int xvm, const int32_t* idx, const float* dpre, int dpvm, float* dw,
+// (xvm / dpvm; the small-channel kernels are batch-major only).  `code`:
+// CFSD_DW_PLAIN, or CFSD_DW_VM32 (vm32_shape() with both operands
+// vertex-major: a many-row layer then takes vm32::conv_dw_vm32).
+static int dw_f32(int code, const float* x, int xvm, const int32_t* idx, const float* dpre, int dpvm, float* dw,
                   float* db, float* workspace, size_t workspace_bytes, int batch, int vsrc, int rows,
                   int cin, int cout, hipStream_t st) {
   int rc = CFSD_OK;
@@ -2785,34 +2816,31 @@ static int dw_f32(const float* x, int xvm, const int32_t* idx, const float* dpre
   DwGeom g = dw_geom(batch, rows, cin, cout);
   if (g.kind == kDwNone)
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight: unsupported channels %d -> %d", cin, cout);
-  if ((rc = check_workspace(workspace_bytes, g.ws_floats * sizeof(float)))) return rc;
+  const SlabSet slabs = slab_set(code, batch, vsrc, rows, cin, cout);
+  if ((rc = check_workspace(workspace_bytes, slabs.floats * sizeof(float)))) return rc;
   if ((xvm || dpvm) && g.kind != kDwLat && g.kind != kDwMfma)
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight: vertex-major operands need 32/64 channels");
   if ((long)batch * vsrc * cin >= (1L << 31))
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight: x has >= 2^31 elements (32-bit offsets)");
   const long M = (long)batch * rows;
   if (g.kind == kDwLat || g.kind == kDwMfma) {
-    float* ws_db = workspace + (size_t)g.gx * dw_units(cin, cout) * 1024;
-    int n_slabs;
+    float* ws_db = workspace + slabs.db_off;
     if (g.kind == kDwLat) {
-      n_slabs = lat_slabs(g.gx);
       rc = for_shape(MfmaShapes{}, cin, cout, [&](auto s) {
         using S = decltype(s);
         return launch_dw_lat<S::cin, S::cout>(x, xvm, idx, dpre, dpvm, workspace, ws_db, g, vsrc, rows, batch, st);
       });
-    } else if (dw_vm32_path(xvm, dpvm, cin, cout, batch)) {
-      n_slabs = vm32::dw_slabs(batch, rows, g.gx);
-      rc = vm32::launch_dw(x, idx, dpre, workspace, ws_db, n_slabs, vsrc, rows, batch, st);
+    } else if (code == CFSD_DW_VM32) {
+      rc = vm32::launch_dw(x, idx, dpre, workspace, ws_db, slabs.n_slabs, vsrc, rows, batch, st);
     } else {
-      n_slabs = dw_mfma_slabs(cin, cout, g.gx);
       rc = for_shape(MfmaShapes{}, cin, cout, [&](auto s) {
         using S = decltype(s);
-        return launch_dw_mfma<S::cin, S::cout>(x, xvm, idx, dpre, dpvm, workspace, ws_db, n_slabs, vsrc, rows, batch,
-                                               st);
+        return launch_dw_mfma<S::cin, S::cout>(x, xvm, idx, dpre, dpvm, workspace, ws_db, slabs.n_slabs, vsrc, rows,
+                                               batch, st);
       });
     }
     if (rc) return rc;  // (never kNoShape: dw_geom gives these kinds to the MFMA shapes only)
-    return reduce_dw_units(deferred, cin, cout, workspace, ws_db, dw, db, n_slabs, st);
+    return reduce_slab_set(deferred, slabs, cin, cout, workspace, dw, db, st);
   }
   if (g.kind == kDwInMfma) {
     rc = dw_xyz_in(x, 0, idx, dpre, CFSD_DT_F32, 0, workspace, g.gx, vsrc, rows, batch, cin, cout, st);
@@ -2830,7 +2858,7 @@ static int dw_f32(const float* x, int xvm, const int32_t* idx, const float* dpre
   if (rc == kNoShape)
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight: unsupported channels %d -> %d", cin, cout);
   if (rc) return rc;
-  return reduce_slabs(deferred, cin, cout, workspace, g.gx, dw, db, st);
+  return reduce_slab_set(deferred, slabs, cin, cout, workspace, dw, db, st);
 }
 
 extern "C" int cfsd_spiral_conv_bwd_weight(const float* x, const int32_t* idx, const float* dpre,
@@ -2839,21 +2867,11 @@ extern "C" int cfsd_spiral_conv_bwd_weight(const float* x, const int32_t* idx, c
                                            int seq, int cin, int cout, void* stream) {
   int rc = check_conv_args(x, idx, dpre, batch, vsrc, rows, seq, cin, cout);
   if (rc) return rc;
-  return dw_f32(x, 0, idx, dpre, 0, dw, db, workspace, workspace_bytes, batch, vsrc, rows, cin, cout,
+  return dw_f32(CFSD_DW_PLAIN, x, 0, idx, dpre, 0, dw, db, workspace, workspace_bytes, batch, vsrc, rows, cin, cout,
                 (hipStream_t)stream);
 }
 
 // ---- fused backward (data + weight)
-namespace {
-bool fused_small(int cin, int cout) { return cout * kSeq <= 32 && (cin == 32 || cin == 64); }
-int fused_small_gx(long m_src) {  // ~2 32-row tiles per wave
-  long gx = ((m_src + 31) / 32 + 7) / 8;
-  constexpr int bpc = 0;  // workgroups per CU (0: the occupancy bound)
-  const long cap = bpc > 0 ? (long)bpc * device_cus() : 1024;
-  return (int)(gx > cap ? cap : (gx < 1 ? 1 : gx));
-}
-}  // namespace
-
 namespace {
 // Paired only for 32-wide dpre rows: the 64-wide dx body needs ~256 VGPRs,
 // which would cap the dW workgroups sharing the kernel at 1 wave per SIMD
@@ -2882,9 +2900,7 @@ extern "C" int cfsd_spiral_conv_bwd_paired(int batch, int vsrc, int rows, int se
 extern "C" size_t cfsd_spiral_conv_bwd_workspace(int batch, int vsrc, int rows, int seq, int cin,
                                                  int cout) {
   if (batch <= 0 || vsrc <= 0 || rows <= 0 || seq != kSeq || cin <= 0 || cout <= 0) return 0;
-  if (fused_small(cin, cout))
-    return (size_t)fused_small_gx((long)batch * vsrc) * ((size_t)cout * kSeq * cin + cout) *
-           sizeof(float);
+  if (fused_small(cin, cout)) return slab_set(CFSD_DW_FUSED, batch, vsrc, rows, cin, cout).floats * sizeof(float);
   const size_t a = cfsd_spiral_conv_workspace(batch, vsrc, rows, seq, cin, cout);
   const size_t b = cfsd_spiral_conv_bwd_weight_workspace(batch, rows, seq, cin, cout);
   return a > b ? a : b;
@@ -2898,19 +2914,19 @@ static int bwd_fused_small(const void* x, int x_dt, const float* dpre, int dpvm,
                            const void* elu_y, void* dx, float* dw, float* db, float* workspace, int batch, int vsrc,
                            int rows, int cin, int cout, hipStream_t st) {
   const long Ms = (long)batch * vsrc;
-  const int gx = fused_small_gx(Ms);
+  const SlabSet slabs = slab_set(CFSD_DW_FUSED, batch, vsrc, rows, cin, cout);  // one slab per workgroup
   const int rc = for_shape(FusedSmallShapes{}, cin, cout, [&](auto s) {
     using S = decltype(s);
     return for_storage(x_dt, [&](auto t) {
       using TX = typename decltype(t)::type;
-      hipLaunchKernelGGL((conv_bwd_out_mfma<S::cin, S::cout, TX>), dim3(gx), dim3(256), 0, st, dpre, inv_ptr, inv_row,
-                         (const int4*)inv_head, w, (const TX*)elu_y, (const TX*)x, (TX*)dx, workspace, vsrc, rows, Ms,
-                         batch, vm_of(x_dt), dpvm);
+      hipLaunchKernelGGL((conv_bwd_out_mfma<S::cin, S::cout, TX>), dim3(slabs.n_slabs), dim3(256), 0, st, dpre,
+                         inv_ptr, inv_row, (const int4*)inv_head, w, (const TX*)elu_y, (const TX*)x, (TX*)dx,
+                         workspace, vsrc, rows, Ms, batch, vm_of(x_dt), dpvm);
       return launch_status("spiral_conv_bwd_small");
     });
   });
   if (rc) return rc;
-  return reduce_slabs(!dw, cin, cout, workspace, gx, dw, db, st);
+  return reduce_slab_set(!dw, slabs, cin, cout, workspace, dw, db, st);
 }
 
 extern "C" int cfsd_spiral_conv_bwd(const float* x, const int32_t* idx, const float* dpre,
@@ -2931,19 +2947,21 @@ extern "C" int cfsd_spiral_conv_bwd(const float* x, const int32_t* idx, const fl
   hipStream_t st = (hipStream_t)stream;
   if (dx && bwd_ks_paired(batch, vsrc, rows, cin, cout)) {
     const DwGeom g = dw_geom(batch, rows, cin, cout);
-    float* ws_db = workspace + (size_t)g.gx * dw_units(cin, cout) * 1024;
+    const SlabSet slabs = slab_set(CFSD_DW_FUSED, batch, vsrc, rows, cin, cout);
+    float* ws_db = workspace + slabs.db_off;
     const coarse::DxKsArgs a{dpre, inv_ptr, inv_row, (const int4*)inv_head, w, elu_y, dx, vsrc, rows, batch,
                              (long)batch * vsrc};
     const DwLatArgs d{x, idx, dpre, workspace, ws_db, vsrc, rows, batch * rows, g.rchunk, g.gx, 0, batch, 0, 0};
     rc = coarse::launch_bwd_ks_pair(a, d, lat_tasks(g.gx, dw_units(cin, cout)), cin, cout, st);
     if (rc) return rc;
-    return reduce_dw_units(!dw, cin, cout, workspace, ws_db, dw, db, lat_slabs(g.gx), st);
+    return reduce_slab_set(!dw, slabs, cin, cout, workspace, dw, db, st);
   }
   if (dx && bwd_paired(batch, vsrc, rows, cin, cout)) {
     const DwGeom g = dw_geom(batch, rows, cin, cout);
     const long M = (long)batch * vsrc;
     const long dw_tasks = lat_tasks(g.gx, dw_units(cin, cout));
-    float* ws_db = workspace + (size_t)g.gx * dw_units(cin, cout) * 1024;
+    const SlabSet slabs = slab_set(CFSD_DW_FUSED, batch, vsrc, rows, cin, cout);
+    float* ws_db = workspace + slabs.db_off;
     DxLatArgs a{dpre, inv_ptr, inv_row, (const int4*)inv_head, w, elu_y, dx, vsrc, rows, M, 0};
     DwLatArgs d{x, idx, dpre, workspace, ws_db, vsrc, rows, batch * rows, g.rchunk, g.gx,
                 (int)((dw_tasks + 3) / 4), batch, 0, 0};
@@ -2959,7 +2977,7 @@ extern "C" int cfsd_spiral_conv_bwd(const float* x, const int32_t* idx, const fl
     });
     if (rc == kNoShape) return set_error(CFSD_EINVAL, "spiral_conv_bwd: unsupported channels %d -> %d", cin, cout);
     if (rc) return rc;
-    return reduce_dw_units(!dw, cin, cout, workspace, ws_db, dw, db, lat_slabs(g.gx), st);
+    return reduce_slab_set(!dw, slabs, cin, cout, workspace, dw, db, st);
   }
   if (!fused_small(cin, cout)) {
     if (dx) {
@@ -2981,8 +2999,9 @@ namespace {
 size_t rowsub_dg_floats(int batch, int rows, int cin) {
   return ((size_t)batch * rows * kSeq * cin + 63) / 64 * 64;
 }
+// dG starts behind the layer's dW slabs (vsrc is not read: no small-output layer is a row-subset one)
 size_t rowsub_slab_floats(int batch, int rows, int cin, int cout) {
-  return (dw_geom(batch, rows, cin, cout).ws_floats + 63) / 64 * 64;
+  return (slab_set(CFSD_DW_FUSED, batch, 0, rows, cin, cout).floats + 63) / 64 * 64;
 }
 // 32 input channels (every Enblock after the first in the reference configs;
 // W^T of a 64-channel input would not leave LDS for a second workgroup)
@@ -3059,7 +3078,8 @@ static int bwd_rowsub(const float* x, int xvm, const int32_t* idx, const float* 
   a.n_groups = rowsub_groups((total + 15) / 16, n_tiles);
   a.nb = (int)(((total + 15) / 16 + 3) / 4) * a.n_groups;
   const bool lat = g.kind == kDwLat;
-  float* ws_db = workspace + (size_t)g.gx * dw_units(cin, cout) * 1024;
+  const SlabSet slabs = slab_set(CFSD_DW_FUSED, batch, vsrc, rows, cin, cout);
+  float* ws_db = workspace + slabs.db_off;
   DwLatArgs d{x, idx, dpre, workspace, ws_db, vsrc, rows, total, g.rchunk, g.gx, 0, batch, xvm, 0};
   if (lat) d.nb = (int)((lat_tasks(g.gx, dw_units(cin, cout)) + 3) / 4);
   if (xvm && !lat) return set_error(CFSD_EINVAL, "spiral_conv_bwd_rowsub_x: vertex-major x needs a few-row layer");
@@ -3074,12 +3094,12 @@ static int bwd_rowsub(const float* x, int xvm, const int32_t* idx, const float* 
     rc = vm32::launch_bwd_flat_pair(dpre, inv_flat, flat_width, w, elu_y, dx, xvm, vsrc, rows, batch, cin, cout,
                                     d, lat_tasks(g.gx, dw_units(cin, cout)), st);
     if (rc) return rc;
-    return reduce_dw_units(!dw, cin, cout, workspace, ws_db, dw, db, lat_slabs(g.gx), st);
+    return reduce_slab_set(!dw, slabs, cin, cout, workspace, dw, db, st);
   }
   if ((rc = launch_rowsub_pair(a, d, cin, cout, st))) return rc;
   if (lat) {
-    rc = reduce_dw_units(!dw, cin, cout, workspace, ws_db, dw, db, lat_slabs(g.gx), st);
-  } else {  // many rows: the persistent dW kernel, same slab layout
+    rc = reduce_slab_set(!dw, slabs, cin, cout, workspace, dw, db, st);
+  } else {  // many rows: the persistent dW kernel leaves the same slab set
     rc = cfsd_spiral_conv_bwd_weight(x, idx, dpre, dw, db, workspace, workspace_bytes, batch, vsrc,
                                      rows, seq, cin, cout, stream);
   }
@@ -3323,7 +3343,7 @@ static bool vm_pair_shape(int batch, int rows, int cin, int cout) {
 }
 extern "C" size_t cfsd_spiral_conv_bwd_flat_pair_workspace(int batch, int rows, int seq, int cin, int cout) {
   if (batch <= 0 || rows <= 0 || seq != kSeq || !vm_pair_shape(batch, rows, cin, cout)) return 0;
-  return dw_geom(batch, rows, cin, cout).ws_floats * sizeof(float);
+  return slab_set(CFSD_DW_VM32, batch, 0, rows, cin, cout).floats * sizeof(float);
 }
 
 extern "C" int cfsd_spiral_conv_bwd_flat_pair(const float* x, const int32_t* idx, const float* dpre,
@@ -3347,13 +3367,11 @@ extern "C" int cfsd_spiral_conv_bwd_flat_pair(const float* x, const int32_t* idx
   if ((rc = check_workspace(workspace_bytes, cfsd_spiral_conv_bwd_flat_pair_workspace(batch, rows, seq, cin, cout))))
     return rc;
   hipStream_t st = (hipStream_t)stream;
-  const DwGeom g = dw_geom(batch, rows, cin, cout);
-  float* ws_db = workspace + (size_t)g.gx * dw_units(cin, cout) * 1024;
-  const int nslab = vm32::dw_slabs(batch, rows, g.gx);  // as cfsd_dw_reduce_batch's fused = CFSD_DW_VM32 items
-  rc = vm32::launch_bwd_vm_pair(dpre, inv_flat, flat_width, w, elu_y, dx, x, idx, workspace, ws_db, nslab, vsrc,
-                                rows, batch, st);
+  const SlabSet slabs = slab_set(CFSD_DW_VM32, batch, vsrc, rows, cin, cout);
+  rc = vm32::launch_bwd_vm_pair(dpre, inv_flat, flat_width, w, elu_y, dx, x, idx, workspace, workspace + slabs.db_off,
+                                slabs.n_slabs, vsrc, rows, batch, st);
   if (rc) return rc;
-  return reduce_dw_units(!dw, cin, cout, workspace, ws_db, dw, db, nslab, st);
+  return reduce_slab_set(!dw, slabs, cin, cout, workspace, dw, db, st);
 }
 
 // ---- the bf16 step's Enblock pair (ABI 4.11): row-subset flat dx + vm16 dW slabs
@@ -3371,11 +3389,10 @@ extern "C" int cfsd_spiral_conv_bwd_rowsub_pair_bf16(const void* x, const int32_
   if ((rc = check_flat_width("spiral_conv_bwd_rowsub_pair_bf16", flat_width))) return rc;
   if ((rc = check_inv_aligned(inv_flat, "inv_flat"))) return rc;
   if ((rc = check_dpre_bound(batch, rows, cout, CFSD_DT_F32, kAbsentRow))) return rc;
-  const int nslab = bf::dw_slabs(batch, rows, cin, cout);  // as cfsd_dw_reduce_batch's fused = CFSD_DW_BF16 items
-  if ((rc = check_workspace(workspace_bytes, (size_t)nslab * ((size_t)cout * kSeq * cin + cout) * sizeof(float))))
-    return rc;
+  const SlabSet slabs = slab_set(CFSD_DW_BF16, batch, vsrc, rows, cin, cout);
+  if ((rc = check_workspace(workspace_bytes, slabs.floats * sizeof(float)))) return rc;
   return bf::launch_bwd_rowsub16_pair((const bf16_t*)x, idx, dpre, inv_flat, flat_width, w, (const bf16_t*)elu_y,
-                                      (bf16_t*)dx, workspace, nslab, vsrc, rows, batch, (hipStream_t)stream);
+                                      (bf16_t*)dx, workspace, slabs.n_slabs, vsrc, rows, batch, (hipStream_t)stream);
 }
 
 // ---- the same pair on the bf16 step's tensors (ABI 4.11)
@@ -3392,20 +3409,45 @@ extern "C" int cfsd_spiral_conv_bwd_flat_pair_bf16(const void* x, const int32_t*
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_flat_pair_bf16: 32 -> 32, batch %% 16 == 0 only");
   if ((rc = check_flat_width("spiral_conv_bwd_flat_pair_bf16", flat_width, 20))) return rc;
   if ((rc = check_inv_aligned(inv_flat, "inv_flat"))) return rc;
-  const int nslab = bf::dw_slabs(batch, rows, cin, cout);  // as cfsd_dw_reduce_batch's fused = CFSD_DW_BF16 items
-  if ((rc = check_workspace(workspace_bytes, (size_t)nslab * ((size_t)cout * kSeq * cin + cout) * sizeof(float))))
-    return rc;
+  const SlabSet slabs = slab_set(CFSD_DW_BF16, batch, vsrc, rows, cin, cout);
+  if ((rc = check_workspace(workspace_bytes, slabs.floats * sizeof(float)))) return rc;
   return bf::launch_bwd_vm16_pair((const bf16_t*)x, idx, (const bf16_t*)dpre, inv_flat, flat_width, (const bf16_t*)w,
-                                  (const bf16_t*)elu_y, (bf16_t*)dx, workspace, nslab, vsrc, rows, batch,
+                                  (const bf16_t*)elu_y, (bf16_t*)dx, workspace, slabs.n_slabs, vsrc, rows, batch,
                                   (hipStream_t)stream);
 }
 
 extern "C" size_t cfsd_spiral_conv_bwd_weight_x_workspace(int batch, int rows, int seq, int cin,
                                                           int cout) {
   if (batch <= 0 || rows <= 0 || seq != kSeq || cin <= 0 || cout <= 0) return 0;
-  if (mfma_shape(cin, cout))
-    return (size_t)bf::dw_slabs(batch, rows, cin, cout) * ((size_t)cout * kSeq * cin + cout) * sizeof(float);
+  if (mfma_shape(cin, cout)) return slab_set(CFSD_DW_BF16, batch, 0, rows, cin, cout).floats * sizeof(float);
   return cfsd_spiral_conv_bwd_weight_workspace(batch, rows, seq, cin, cout);
+}
+
+// Which kernels cfsd_spiral_conv_bwd_weight_x runs for these operands, and
+// with them the CFSD_DW_* code of the slabs it leaves.
+namespace {
+enum DwXKind { kDwXNone, kDwXF32, kDwXBf16, kDwXXyzIn };
+struct DwXRoute {
+  DwXKind kind;
+  int code;  // -1 with kDwXNone
+};
+DwXRoute dw_x_route(int x_dt, int dpre_dt, int batch, int cin, int cout) {
+  const DwXRoute none{kDwXNone, -1};
+  if (batch <= 0 || cin <= 0 || cout <= 0 || !dt_ok(x_dt) || !dt_ok(dpre_dt)) return none;
+  const int xt = CFSD_DT_TYPE(x_dt);
+  if (mfma_shape(cin, cout) && xt == CFSD_DT_F32) {  // the fp32 kernels (dw_f32), x / dpre in any layout
+    if (CFSD_DT_TYPE(dpre_dt) != CFSD_DT_F32) return none;
+    const bool vm = vm_of(x_dt) && vm_of(dpre_dt) && vm32_shape(batch, cin, cout);
+    return {kDwXF32, vm ? CFSD_DW_VM32 : CFSD_DW_PLAIN};
+  }
+  if (mfma_shape(cin, cout) && xt == CFSD_DT_BF16) return {kDwXBf16, CFSD_DW_BF16};
+  if (cin <= 3 && (cout == 32 || cout == 64) && xt == CFSD_DT_F32) return {kDwXXyzIn, CFSD_DW_PLAIN};
+  return none;
+}
+}  // namespace
+
+extern "C" int cfsd_spiral_conv_bwd_weight_x_slabs(int x_dt, int dpre_dt, int batch, int cin, int cout) {
+  return dw_x_route(x_dt, dpre_dt, batch, cin, cout).code;
 }
 
 extern "C" int cfsd_spiral_conv_bwd_weight_x(const void* x, int x_dt, const int32_t* idx,
@@ -3423,29 +3465,23 @@ extern "C" int cfsd_spiral_conv_bwd_weight_x(const void* x, int x_dt, const int3
     return rc;
   const hipStream_t st = (hipStream_t)stream;
   const int xvm = vm_of(x_dt), dpvm = vm_of(dpre_dt);
-  x_dt = CFSD_DT_TYPE(x_dt);
-  int n_slabs = 0;
-  if (mfma_shape(cin, cout) && x_dt == CFSD_DT_F32) {  // fp32: the fp32 kernels, x / dpre in any layout
-    if (CFSD_DT_TYPE(dpre_dt) != CFSD_DT_F32)
-      return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight_x: fp32 x needs fp32 dpre");
-    return dw_f32((const float*)x, xvm, idx, (const float*)dpre, dpvm, dw, db, workspace, workspace_bytes, batch,
-                  vsrc, rows, cin, cout, st);
-  }
-  if (mfma_shape(cin, cout) && x_dt == CFSD_DT_BF16) {
+  const DwXRoute r = dw_x_route(x_dt, dpre_dt, batch, cin, cout);
+  if (r.kind == kDwXNone)
+    return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight_x: unsupported %d -> %d with dtypes %d/%d (fp32 x: fp32 dpre)",
+                     cin, cout, x_dt, dpre_dt);
+  if (r.kind == kDwXF32)
+    return dw_f32(r.code, (const float*)x, xvm, idx, (const float*)dpre, dpvm, dw, db, workspace, workspace_bytes,
+                  batch, vsrc, rows, cin, cout, st);
+  const SlabSet slabs = slab_set(r.code, batch, vsrc, rows, cin, cout);
+  if (r.kind == kDwXBf16) {
     rc = bf::launch_dw((const bf16_t*)x, xvm, idx, dpre, dpre_dt, workspace, vsrc, rows, (long)batch * rows, cin,
                        cout, st);
-    n_slabs = bf::dw_slabs(batch, rows, cin, cout);
-  } else if (cin <= 3 && (cout == 32 || cout == 64) && x_dt == CFSD_DT_F32) {
-    const DwGeom g = dw_geom(batch, rows, cin, cout);
-    if (g.kind != kDwInMfma) return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight_x: geometry");
-    rc = dw_xyz_in((const float*)x, xvm, idx, dpre, dpre_dt, dpvm, workspace, g.gx, vsrc, rows, batch, cin, cout, st);
-    n_slabs = g.gx;
-  } else {
-    return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight_x: unsupported %d -> %d with dtypes %d/%d", cin,
-                     cout, x_dt, dpre_dt);
+  } else {  // the xyz input layer: one slab per workgroup of dw_geom's kDwInMfma grid
+    rc = dw_xyz_in((const float*)x, xvm, idx, dpre, dpre_dt, dpvm, workspace, dw_geom(batch, rows, cin, cout).gx, vsrc,
+                   rows, batch, cin, cout, st);
   }
   if (rc) return rc;
-  return reduce_slabs(!dw, cin, cout, workspace, n_slabs, dw, db, st);
+  return reduce_slab_set(!dw, slabs, cin, cout, workspace, dw, db, st);
 }
 
 extern "C" int cfsd_spiral_conv_bwd_x(const void* x, int x_dt, const int32_t* idx, const float* dpre,
@@ -3493,53 +3529,31 @@ extern "C" int cfsd_spiral_conv_bwd_out_flat(const void* x, int x_dt, const int3
   if ((rc = check_workspace(workspace_bytes, cfsd_spiral_conv_bwd_workspace(batch, vsrc, rows, seq, cin, cout))))
     return rc;
   const hipStream_t st = (hipStream_t)stream;
-  const int gx = fused_small_gx((long)batch * vsrc);
+  const SlabSet slabs = slab_set(CFSD_DW_FUSED, batch, vsrc, rows, cin, cout);  // one slab per workgroup
   rc = vm32::launch_bwd_out(dpre, inv_flat, flat_width, w, elu_y, x, dx, CFSD_DT_TYPE(x_dt) == CFSD_DT_BF16,
-                            workspace, gx, vsrc, rows, batch, st);
+                            workspace, slabs.n_slabs, vsrc, rows, batch, st);
   if (rc) return rc;
-  return reduce_slabs(!dw, cin, cout, workspace, gx, dw, db, st);
+  return reduce_slab_set(!dw, slabs, cin, cout, workspace, dw, db, st);
 }
 
-// Slab geometry of one deferred weight-gradient item (kind, slab count,
-// slab length, db partials): what the producing launch chose.
+// One deferred weight-gradient item of the batched reduce: its slab set is
+// slab_set() of the code and sizes it carries.
 template <typename Item>
 static int fill_red_item(const cfsd_dw_slabs& q, int i, Item& d) {
   if (!q.workspace || !q.dw || !q.db) return set_error(CFSD_EINVAL, "dw_reduce_batch: item %d null", i);
   if (q.batch <= 0 || q.rows <= 0 || q.vsrc <= 0 || q.cin <= 0 || q.cout <= 0)
     return set_error(CFSD_EINVAL, "dw_reduce_batch: item %d bad sizes", i);
+  const SlabSet s = slab_set(q.fused, q.batch, q.vsrc, q.rows, q.cin, q.cout);
+  if (s.n_slabs == 0) return set_error(CFSD_EINVAL, "dw_reduce_batch: item %d unsupported channels", i);
   d.ws = q.workspace;
-  d.ws_db = nullptr;
+  d.ws_db = s.unit ? q.workspace + s.db_off : nullptr;
   d.dw = q.dw;
   d.db = q.db;
   d.cin = q.cin;
   d.cout = q.cout;
-  const int K = kSeq * q.cin;
-  if (q.fused == CFSD_DW_BF16 && mfma_shape(q.cin, q.cout)) {  // bf16 MFMA dW: plain slabs
-    d.kind = 1;
-    d.n_slabs = bf::dw_slabs(q.batch, q.rows, q.cin, q.cout);
-    d.n_el = q.cout * K + q.cout;
-  } else if (q.fused != CFSD_DW_PLAIN && fused_small(q.cin, q.cout)) {
-    d.kind = 1;
-    d.n_slabs = fused_small_gx((long)q.batch * q.vsrc);
-    d.n_el = q.cout * K + q.cout;
-  } else {
-    const DwGeom g = dw_geom(q.batch, q.rows, q.cin, q.cout);
-    if (g.kind == kDwNone) return set_error(CFSD_EINVAL, "dw_reduce_batch: item %d unsupported channels", i);
-    if (g.kind == kDwMfma || g.kind == kDwLat) {
-      const int U = (int)dw_units(q.cin, q.cout);
-      d.kind = 0;
-      const bool vm = q.fused == CFSD_DW_VM32 && dw_vm32_path(1, 1, q.cin, q.cout, q.batch);  // as dw_f32 chose
-      d.n_slabs = g.kind == kDwLat ? lat_slabs(g.gx)
-                  : vm             ? vm32::dw_slabs(q.batch, q.rows, g.gx)
-                                   : dw_mfma_slabs(q.cin, q.cout, g.gx);
-      d.n_el = U * 1024 + q.cout;
-      d.ws_db = q.workspace + (size_t)g.gx * U * 1024;
-    } else {
-      d.kind = 1;
-      d.n_slabs = g.gx;
-      d.n_el = q.cout * K + q.cout;
-    }
-  }
+  d.kind = s.unit ? 0 : 1;
+  d.n_slabs = s.n_slabs;
+  d.n_el = s.n_el;
   return CFSD_OK;
 }
 

@@ -282,9 +282,7 @@ def spiral_conv_bwd_weight(x, idx, dpre, dw, db, workspace, general=False):
         return DeferredGenDw(workspace, bsz, rows, seq, cin, cout) if dw is None else None
     call("cfsd_spiral_conv_bwd_weight", ptr(x), ptr(idx), ptr(dpre), ptr(dw), ptr(db),
          ptr(workspace), ctypes.c_size_t(nbytes), bsz, vsrc, rows, seq, cin, cout, stream_ptr())
-    if dw is None:
-        return DeferredDw(workspace, bsz, vsrc, rows, cin, cout, DW_PLAIN)
-    return None
+    return _deferred(dw, workspace, bsz, vsrc, rows, cin, cout, DW_PLAIN)
 
 
 class DeferredDw:
@@ -298,6 +296,18 @@ class DeferredDw:
         _need(dw, (self.sizes[4], 9 * self.sizes[3]), name="dw")
         _need(db, (self.sizes[4],), name="db")
         return _abi.DwSlabs(self.workspace.data_ptr(), dw.data_ptr(), db.data_ptr(), *self.sizes)
+
+
+def _deferred(dw, workspace, bsz, vsrc, rows, cin, cout, code):
+    """What a weight-gradient call returns for its dW: the reduction was
+    deferred iff ``dw is None``, and then the slabs in ``workspace`` are
+    described by the entry point's ``CFSD_DW_*`` code; None when it reduced."""
+    return DeferredDw(workspace, bsz, vsrc, rows, cin, cout, code) if dw is None else None
+
+
+def _with_dx(dx, d):
+    """What a dx + dW call returns: ``dx``, or ``(dx, d)`` when it deferred the weight gradient."""
+    return dx if d is None else (dx, d)
 
 
 class DeferredGenDw:
@@ -379,13 +389,11 @@ def spiral_conv_bwd(x, idx, dpre, inv, w, dw, db, dx=None, elu_y=None, workspace
         if dx is not None:
             spiral_conv_bwd_data(dpre, inv, w, vsrc, elu_y=elu_y, out=dx)
         d = spiral_conv_bwd_weight(x, idx, dpre, dw, db, ws)
-        return (dx, d) if dw is None else dx
+        return _with_dx(dx, d)
     call("cfsd_spiral_conv_bwd", ptr(x), ptr(idx), ptr(dpre), ptr(inv_ptr), ptr(inv_row),
          ptr(inv_head), ptr(w), ptr(elu_y), ptr(dx), ptr(dw), ptr(db), ptr(ws), ctypes.c_size_t(nb),
          bsz, vsrc, rows, seq, cin, cout, stream_ptr())
-    if dw is None:  # deferred weight gradient
-        return dx, DeferredDw(ws, bsz, vsrc, rows, cin, cout, DW_FUSED)
-    return dx
+    return _with_dx(dx, _deferred(dw, ws, bsz, vsrc, rows, cin, cout, DW_FUSED))
 
 
 def spiral_conv_bwd_rowsub_workspace(bsz, vsrc, rows, seq, cin, cout):
@@ -417,9 +425,7 @@ def spiral_conv_bwd_rowsub(x, idx, dpre, flat, w, dw, db, dx, elu_y=None, worksp
         call("cfsd_spiral_conv_bwd_rowsub_x", ptr(x), _st(x), *rest)
     else:
         call("cfsd_spiral_conv_bwd_rowsub", ptr(x), *rest)
-    if dw is None:  # deferred weight gradient (slabs at the workspace start)
-        return dx, DeferredDw(ws, bsz, vsrc, rows, cin, cout, DW_FUSED)
-    return dx
+    return _with_dx(dx, _deferred(dw, ws, bsz, vsrc, rows, cin, cout, DW_FUSED))  # slabs at the workspace start
 
 
 def spiral_conv_bwd_data_rowsub_workspace(bsz, rows, seq, cin):
@@ -1896,13 +1902,9 @@ def spiral_conv_bwd_weight_x(x, idx, dpre, dw, db, workspace):
                                  spiral_conv_bwd_weight_x_workspace(bsz, rows, seq, cin, cout, x.dtype))
     call("cfsd_spiral_conv_bwd_weight_x", ptr(x), _st(x), ptr(idx), ptr(dpre), _st(dpre), ptr(dw), ptr(db),
          ptr(workspace), ctypes.c_size_t(nbytes), bsz, vsrc, rows, seq, cin, cout, stream_ptr())
-    if dw is None:  # bf16 32/64-channel slabs are plain (DW_BF16); fp32 x: the fp32 kernels' slabs
-        mfma = cin in (32, 64) and cout in (32, 64) and x.dtype == torch.bfloat16
-        # fp32 32 -> 32 with vertex-major x and dpre: conv_dw_vm32's slabs (DW_VM32)
-        vm32 = (x.dtype == torch.float32 and is_vm(x) and is_vm(dpre) and cin == 32 and cout == 32
-                and bsz % 16 == 0)
-        return DeferredDw(workspace, bsz, vsrc, rows, cin, cout, DW_BF16 if mfma else (DW_VM32 if vm32 else DW_PLAIN))
-    return None
+    # the code is the library's own routing decision for these operands
+    code = _abi.lib().cfsd_spiral_conv_bwd_weight_x_slabs(_st(x), _st(dpre), bsz, cin, cout)
+    return _deferred(dw, workspace, bsz, vsrc, rows, cin, cout, code)
 
 
 def spiral_conv_bwd_flat_pair_workspace(bsz, rows, seq, cin, cout):
@@ -1929,9 +1931,7 @@ def spiral_conv_bwd_flat_pair(x, idx, dpre, flat, w, dw, db, dx, elu_y=None, wor
     ws, nb = _conv_ws(workspace, x.device, need)
     call("cfsd_spiral_conv_bwd_flat_pair", ptr(x), ptr(idx), ptr(dpre), ptr(table), width, ptr(w), ptr(elu_y),
          ptr(dx), ptr(dw), ptr(db), ptr(ws), ctypes.c_size_t(nb), bsz, vsrc, rows, seq, cin, cout, stream_ptr())
-    if dw is None:
-        return DeferredDw(ws, bsz, vsrc, rows, cin, cout, DW_VM32)
-    return None
+    return _deferred(dw, ws, bsz, vsrc, rows, cin, cout, DW_VM32)
 
 
 def spiral_conv_bwd_flat_pair_bf16(x, idx, dpre, flat, w16, dx, elu_y=None, workspace=None):
@@ -1952,7 +1952,7 @@ def spiral_conv_bwd_flat_pair_bf16(x, idx, dpre, flat, w16, dx, elu_y=None, work
     call("cfsd_spiral_conv_bwd_flat_pair_bf16", ptr(x), ptr(idx), ptr(dpre), ptr(table), width, ptr(w16),
          ptr(elu_y), ptr(dx), ptr(workspace), ctypes.c_size_t(nbytes), bsz, vsrc, rows, seq, cin, cout,
          stream_ptr())
-    return DeferredDw(workspace, bsz, vsrc, rows, cin, cout, DW_BF16)
+    return _deferred(None, workspace, bsz, vsrc, rows, cin, cout, DW_BF16)
 
 
 def spiral_conv_bwd_rowsub_pair_bf16(x, idx, dpre, flat, w, dx, elu_y=None, workspace=None):
@@ -1974,7 +1974,7 @@ def spiral_conv_bwd_rowsub_pair_bf16(x, idx, dpre, flat, w, dx, elu_y=None, work
     call("cfsd_spiral_conv_bwd_rowsub_pair_bf16", ptr(x), ptr(idx), ptr(dpre), ptr(table), width, ptr(w),
          ptr(elu_y), ptr(dx), ptr(workspace), ctypes.c_size_t(nbytes), bsz, vsrc, rows, seq, cin, cout,
          stream_ptr())
-    return DeferredDw(workspace, bsz, vsrc, rows, cin, cout, DW_BF16)
+    return _deferred(None, workspace, bsz, vsrc, rows, cin, cout, DW_BF16)
 
 
 def spiral_conv_bwd_x(x, idx, dpre, inv, w, dw, db, dx=None, elu_y=None, workspace=None):
@@ -1994,9 +1994,7 @@ def spiral_conv_bwd_x(x, idx, dpre, inv, w, dw, db, dx=None, elu_y=None, workspa
     call("cfsd_spiral_conv_bwd_x", ptr(x), _st(x), ptr(idx), ptr(dpre), _st(dpre), ptr(inv_ptr), ptr(inv_row),
          ptr(inv_head), ptr(w), ptr(elu_y), ptr(dx), ptr(dw), ptr(db), ptr(ws), ctypes.c_size_t(nb),
          bsz, vsrc, rows, seq, cin, cout, stream_ptr())
-    if dw is None:
-        return dx, DeferredDw(ws, bsz, vsrc, rows, cin, cout, DW_FUSED)
-    return dx
+    return _with_dx(dx, _deferred(dw, ws, bsz, vsrc, rows, cin, cout, DW_FUSED))
 
 
 def spiral_conv_bwd_out_flat(x, idx, dpre, flat, w, dw, db, dx=None, elu_y=None, workspace=None):
@@ -2015,9 +2013,7 @@ def spiral_conv_bwd_out_flat(x, idx, dpre, flat, w, dw, db, dx=None, elu_y=None,
     call("cfsd_spiral_conv_bwd_out_flat", ptr(x), _st(x), ptr(idx), ptr(dpre), _st(dpre), ptr(table), width,
          ptr(w), ptr(elu_y), ptr(dx), ptr(dw), ptr(db), ptr(ws), ctypes.c_size_t(nb), bsz, vsrc, rows, seq, cin,
          cout, stream_ptr())
-    if dw is None:
-        return dx, DeferredDw(ws, bsz, vsrc, rows, cin, cout, DW_FUSED)
-    return dx
+    return _with_dx(dx, _deferred(dw, ws, bsz, vsrc, rows, cin, cout, DW_FUSED))
 
 
 def spmm_x(csr, x, m, elu_y=None, out=None, order=None, uniform=0, sched=None):

@@ -106,15 +106,44 @@ size_t cfsd_spiral_conv_bwd_weight_workspace(int batch, int rows, int seq, int c
  * called with dw == db == NULL leave their per-workgroup partial sums in
  * `workspace` and skip the reduction; cfsd_dw_reduce_batch then reduces up
  * to CFSD_DW_REDUCE_MAX such layers (each with its own workspace) in ONE
- * launch, with the same fixed summation order (identical results).  `fused`
- * is one of the CFSD_DW_* codes: which launch left the partials. */
+ * launch, with the same fixed summation order (identical results).
+ *
+ * The slabs' layout is a function of (fused, batch, vsrc, rows, cin, cout)
+ * alone; the library derives it in one place, for the producing launch, its
+ * workspace query and both reduces.  `fused` is one of the CFSD_DW_* codes.
+ * Two layouts exist.  UNIT slabs (32/64 -> 32/64 channels, fp32 kernels): per
+ * slab 9*(cin/32)*(cout/32) units of 1024 floats, the db partials of all
+ * slabs behind the last unit.  PLAIN slabs: per slab [cout x 9 cin | cout]
+ * floats.  What a code selects:
+ *   CFSD_DW_PLAIN  the fp32 weight-gradient kernels' slabs: unit slabs for
+ *                  32/64 -> 32/64 channels (few-row kernel below 65536 =
+ *                  batch x rows, persistent kernel from there), plain slabs
+ *                  for the xyz input (cin <= 4) and output (cout <= 4) layers.
+ *                  Left by cfsd_spiral_conv_bwd_weight, and by
+ *                  cfsd_spiral_conv_bwd_weight_x on the xyz input layer or
+ *                  on fp32 x (but see CFSD_DW_VM32).
+ *   CFSD_DW_FUSED  a dx + dW call.  For a small-output layer (cout*seq <= 32,
+ *                  cin 32/64) the fused kernel's own plain slabs, counted
+ *                  from batch x vsrc: cfsd_spiral_conv_bwd, _bwd_x,
+ *                  _bwd_out_flat.  For every other shape the same as
+ *                  CFSD_DW_PLAIN: cfsd_spiral_conv_bwd, _bwd_rowsub(_x).
+ *   CFSD_DW_BF16   32/64 -> 32/64 channels: the bf16 MFMA kernels' plain
+ *                  slabs.  Left by cfsd_spiral_conv_bwd_weight_x on bf16 x
+ *                  and by the two *_pair_bf16 calls.  Any other shape: as
+ *                  CFSD_DW_FUSED.
+ *   CFSD_DW_VM32   32 -> 32, batch % 16 == 0, batch x rows >= 65536: the
+ *                  vertex-major fp32 kernel's unit slabs (its own count).
+ *                  Left by cfsd_spiral_conv_bwd_weight_x with fp32
+ *                  vertex-major x and dpre (ABI 4.3) and by
+ *                  cfsd_spiral_conv_bwd_flat_pair (ABI 4.10).  Any other
+ *                  shape: as CFSD_DW_FUSED.
+ * cfsd_spiral_conv_bwd_weight_x is the one entry point whose code depends on
+ * its operands: cfsd_spiral_conv_bwd_weight_x_slabs() below returns it. */
 #define CFSD_DW_REDUCE_MAX 16
-#define CFSD_DW_PLAIN 0 /* cfsd_spiral_conv_bwd_weight; _bwd_weight_x on fp32 x or the xyz input layer */
-#define CFSD_DW_FUSED 1 /* a dx + dW call: cfsd_spiral_conv_bwd(_x) (small-output layers, cout*seq <= 32:
-                           their own slabs), _bwd_out_flat, _bwd_rowsub(_x) */
-#define CFSD_DW_BF16 2  /* cfsd_spiral_conv_bwd_weight_x on a 32/64-channel bf16 layer; the *_pair_bf16 calls */
-#define CFSD_DW_VM32 3  /* cfsd_spiral_conv_bwd_weight_x on a 32 -> 32 fp32 layer with vertex-major x and
-                           dpre, batch % 16 == 0 (ABI 4.3); cfsd_spiral_conv_bwd_flat_pair (ABI 4.10) */
+#define CFSD_DW_PLAIN 0
+#define CFSD_DW_FUSED 1
+#define CFSD_DW_BF16 2
+#define CFSD_DW_VM32 3
 typedef struct {
   const float* workspace;
   float* dw;
@@ -615,14 +644,20 @@ int cfsd_spiral_conv_bwd_data_flat(const void* dpre, int dpre_dt, const int32_t*
                                    int cout, void* stream);
 /* dW/db (fp32): 32/64-channel layers (x bf16, dpre bf16/fp32; or x and dpre
  * fp32, each batch-major or vertex-major) and the xyz input layer (x fp32,
- * dpre bf16 or fp32).  dw == db == NULL defers the reduction
- * (cfsd_dw_reduce_batch item with fused = CFSD_DW_BF16 for the bf16 32/64-channel kind,
- * CFSD_DW_PLAIN for fp32 x and for the input layer). */
+ * dpre bf16 or fp32).  dw == db == NULL defers the reduction: the
+ * cfsd_dw_reduce_batch item's `fused` is what cfsd_spiral_conv_bwd_weight_x_slabs
+ * returns for the same operands. */
 size_t cfsd_spiral_conv_bwd_weight_x_workspace(int batch, int rows, int seq, int cin, int cout);
 int cfsd_spiral_conv_bwd_weight_x(const void* x, int x_dt, const int32_t* idx, const void* dpre,
                                   int dpre_dt, float* dw, float* db, float* workspace,
                                   size_t workspace_bytes, int batch, int vsrc, int rows, int seq,
                                   int cin, int cout, void* stream);
+/* The CFSD_DW_* code of the slabs a deferred cfsd_spiral_conv_bwd_weight_x
+ * call with these operands leaves (ABI 4.20), or -1 where the entry point
+ * refuses the combination of storage types and channels.  It is the entry
+ * point's own routing decision; a pure function of its arguments (no device
+ * call: usable during graph capture and without a GPU). */
+int cfsd_spiral_conv_bwd_weight_x_slabs(int x_dt, int dpre_dt, int batch, int cin, int cout);
 /* Fused dx + dW of the xyz output layer (cout*seq <= 32) with x, elu_y, dx
  * bf16 (or all three fp32, ABI 4.1) and dpre fp32 (workspace:
  * cfsd_spiral_conv_bwd_workspace; deferred items use fused = CFSD_DW_FUSED).  x_dt's

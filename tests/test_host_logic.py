@@ -148,6 +148,34 @@ def test_conv_entry_points_reject_before_launch(lib):
             assert b"workspace" in msg
 
 
+def test_bwd_weight_x_slabs_code(lib):
+    """cfsd_spiral_conv_bwd_weight_x_slabs: the CFSD_DW_* code a deferred
+    cfsd_spiral_conv_bwd_weight_x leaves, -1 where the entry point refuses the
+    operands.  A pure function (no device call), so it runs here."""
+    F32, BF16, VM = 0, 1, 0x10
+    PLAIN, BF16_SLABS, VM32 = (_abi.CONSTANTS["CFSD_DW_" + k] for k in ("PLAIN", "BF16", "VM32"))
+    table = [
+        ((F32 | VM, F32 | VM, 16, 32, 32), VM32),        # vertex-major fp32 32 -> 32, 16-mesh batches
+        ((F32 | VM, F32, 16, 32, 32), PLAIN),            # ... needs both operands vertex-major
+        ((F32 | VM, F32 | VM, 4, 32, 32), PLAIN),        # ... and batch % 16 == 0
+        ((F32 | VM, F32 | VM, 16, 32, 64), PLAIN),       # ... and 32 -> 32
+        ((F32, F32, 16, 64, 64), PLAIN),
+        ((BF16 | VM, BF16 | VM, 16, 32, 32), BF16_SLABS),  # bf16 x: the bf16 MFMA kernels, dpre bf16 or fp32
+        ((BF16, F32, 4, 64, 32), BF16_SLABS),
+        ((F32, BF16, 16, 3, 32), PLAIN),                 # the xyz input layer, dpre bf16 or fp32
+        ((F32 | VM, F32, 16, 3, 64), PLAIN),
+        ((F32 | VM, BF16 | VM, 16, 32, 32), -1),         # fp32 x needs fp32 dpre
+        ((BF16, BF16, 16, 32, 3), -1),                   # no _x weight gradient for the output layer
+        ((BF16, BF16, 16, 3, 32), -1),                   # the input layer's x is fp32
+        ((2, F32, 16, 32, 32), -1),                      # not a storage type
+        ((F32, F32 | 0x20, 16, 32, 32), -1),             # an unknown flag
+        ((F32, F32, 0, 32, 32), -1),
+    ]
+    for args, want in table:
+        assert lib.cfsd_spiral_conv_bwd_weight_x_slabs(*args) == want, args
+    assert (PLAIN, BF16_SLABS, VM32) == (0, 2, 3)
+
+
 def test_inverse_spiral_matches_bruteforce():
     rs = np.random.RandomState(0)
     idx = rs.randint(0, 50, size=(80, 9))
