@@ -3160,8 +3160,11 @@ extern "C" int cfsd_spiral_conv_bwd_data_rowsub(const float* dpre, const int32_t
     if (dx_dt == CFSD_DT_BF16)
       return vm32::launch_dx_flat_b16(dpre, inv_flat, flat_width, w, (const bf16_t*)elu_y, (bf16_t*)dx, dxvm, vsrc,
                                       rows, batch, cin, cout, st);
-    return vm32::launch_dx_flat(dpre, 0, dxvm, inv_flat, flat_width, w, (const float*)elu_y, (float*)dx, vsrc, rows,
-                                batch, cin, cout, st);
+    // (fp32 dx: no width-4 instance of the flat-list kernel; such a table takes the dG path below,
+    // as it does in cfsd_spiral_conv_bwd_rowsub)
+    if (flat_width != 4)
+      return vm32::launch_dx_flat(dpre, 0, dxvm, inv_flat, flat_width, w, (const float*)elu_y, (float*)dx, vsrc, rows,
+                                  batch, cin, cout, st);
   }
   const int total = batch * rows;
   DgArgs a{dpre, w, workspace, total, rowsub_groups((total + 15) / 16, kSeq * cin / 16), 0};

@@ -27,109 +27,15 @@ import numpy as np
 import pytest
 import torch
 
-import cfsd_loader
+from conv_cases import DEV, Case, check, check_case, gamma, run_kernels  # (loads libcfsd)
+from craniofacialsd_vae_amd import model as M
+from craniofacialsd_vae_amd import ops, topology
 
 pytestmark = pytest.mark.gpu
 
-cfsd_loader.load()
-from craniofacialsd_vae_amd import model as M  # noqa: E402
-from craniofacialsd_vae_amd import ops, topology  # noqa: E402
-from craniofacialsd_vae_amd.ops import ACT_ELU, ACT_NONE  # noqa: E402
-
-DEV = "cuda"
-U = 2.0 ** -24
 SHAPES = [(1, 1, 1), (7, 3, 8), (12, 8, 20), (4, 20, 3), (5, 40, 36), (9, 48, 32)]
 GEOMS = [(70, 70), (70, 37), (9, 5)]
 BATCHES = (1, 3)
-
-
-def gamma(n):
-    n = torch.as_tensor(n, dtype=torch.float64)
-    return n * U / (1 - n * U)
-
-
-class Case:
-    """Inputs of one conv (host fp32 + device copies) and its fp64 restatement."""
-
-    def __init__(self, batch, vsrc, rows, seq, cin, cout, seed):
-        g = torch.Generator().manual_seed(seed)
-        self.shape = (batch, vsrc, rows, seq, cin, cout)
-        idx = torch.randint(0, vsrc, (rows, seq), generator=g)  # with replacement
-        self.absent = vsrc - 1                                  # a vertex that is in no spiral
-        idx[idx == self.absent] = 0
-        self.idx = idx
-        self.x = torch.randn(batch, vsrc, cin, generator=g)
-        self.w = torch.randn(cout, seq * cin, generator=g)
-        self.b = torch.randn(cout, generator=g)
-        self.dpre = torch.randn(batch, rows, cout, generator=g)
-        # ELU outputs as the forward kernels produce them: fl(fl(exp(v)) - 1) for v <= 0
-        v = torch.randn(batch, vsrc, cin, generator=g)
-        self.elu_y = torch.where(v > 0, v, torch.exp(v) - 1.0)
-        inv = topology.inverse_spiral(idx.numpy(), vsrc)
-        self.d = {k: getattr(self, k).to(DEV) for k in ("x", "w", "b", "dpre", "elu_y")}
-        self.d["idx"] = idx.to(torch.int32).to(DEV)
-        self.inv = tuple(torch.from_numpy(a).to(DEV) for a in inv)
-        self._ref()
-
-    def _ref(self):
-        batch, vsrc, rows, seq, cin, cout = self.shape
-        x, w, b, dp = self.x.double(), self.w.double(), self.b.double(), self.dpre.double()
-        flat = self.idx.reshape(-1)
-        G = x[:, flat].reshape(batch, rows, seq * cin)
-        self.pre = G @ w.T + b
-        self.pre_abs = G.abs() @ w.abs().T + b.abs()
-        self.n_fwd = seq * cin + 1
-        dG = (dp @ w).reshape(batch, rows * seq, cin)
-        dG_abs = (dp.abs() @ w.abs()).reshape(batch, rows * seq, cin)
-        self.dx = torch.zeros(batch, vsrc, cin, dtype=torch.float64).index_add_(1, flat, dG)
-        self.dx_abs = torch.zeros(batch, vsrc, cin, dtype=torch.float64).index_add_(1, flat, dG_abs)
-        self.n_dx = (torch.bincount(flat, minlength=vsrc) * cout).double().view(1, vsrc, 1)
-        y = self.elu_y.double()
-        self.g = torch.where(y > 0, torch.ones_like(y), y + 1)
-        G2, dp2 = G.reshape(batch * rows, -1), dp.reshape(batch * rows, cout)
-        self.dw, self.dw_abs = dp2.T @ G2, dp2.abs().T @ G2.abs()
-        self.db, self.db_abs = dp2.sum(0), dp2.abs().sum(0)
-        self.n_dw = batch * rows
-
-
-def check(name, got, ref, tol, shape):
-    err = (got.double().cpu() - ref).abs()
-    worst = float((err / tol.clamp_min(1e-300)).max()) if err.numel() else 0.0
-    print(f"{name} {shape}: max err {float(err.max()):.3e}, max err/bound {worst:.3f}")
-    bad = err > tol
-    assert not bool(bad.any()), (name, shape, float(err.max()), worst, int(bad.sum()))
-
-
-def run_kernels(c, general=False):
-    """Every product of case ``c`` through ops (the general family where the
-    shape has no instance, or everywhere with ``general``)."""
-    batch, vsrc, rows, seq, cin, cout = c.shape
-    d, kw = c.d, {"general": True} if general else {}
-    out = {}
-    out["y_none"] = ops.spiral_conv_fwd(d["x"], d["idx"], d["w"], d["b"], ACT_NONE, **kw)
-    out["y_elu"] = ops.spiral_conv_fwd(d["x"], d["idx"], d["w"], d["b"], ACT_ELU, **kw)
-    out["dx"] = ops.spiral_conv_bwd_data(d["dpre"], c.inv, d["w"], vsrc, **kw)
-    out["dx_elu"] = ops.spiral_conv_bwd_data(d["dpre"], c.inv, d["w"], vsrc, elu_y=d["elu_y"], **kw)
-    need = ops.spiral_conv_bwd_weight_workspace(batch, rows, seq, cin, cout, **kw)
-    assert need > 0
-    ws = torch.empty(need // 4, dtype=torch.float32, device=DEV)
-    out["dw"], out["db"] = torch.empty_like(d["w"]), torch.empty_like(d["b"])
-    assert ops.spiral_conv_bwd_weight(d["x"], d["idx"], d["dpre"], out["dw"], out["db"], ws, **kw) is None
-    return out, ws
-
-
-def check_case(c, out):
-    s = c.shape
-    tol = gamma(c.n_fwd) * c.pre_abs
-    check("fwd", out["y_none"], c.pre, tol, s)
-    ref = torch.where(c.pre > 0, c.pre, torch.expm1(c.pre))
-    check("fwd+elu", out["y_elu"], ref, tol + U * ref.abs().clamp_min(1.0), s)
-    tol = gamma(c.n_dx) * c.dx_abs
-    check("dx", out["dx"], c.dx, tol, s)
-    ref = c.g * c.dx
-    check("dx*elu'", out["dx_elu"], ref, c.g * tol + U * (ref.abs() + c.g * tol), s)
-    check("dw", out["dw"], c.dw, gamma(c.n_dw) * c.dw_abs, s)
-    check("db", out["db"], c.db, gamma(c.n_dw) * c.db_abs, s)
 
 
 @pytest.mark.parametrize("vsrc,rows", GEOMS)
