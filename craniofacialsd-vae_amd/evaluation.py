@@ -13,13 +13,14 @@ leave the device before they are final.
 What replaces the reference's output files: mp4 videos become animated PNGs
 (``rendering.save_apng``; same frames, same rates), the seaborn plots of the
 traversal become ``latent_exploration.json`` (the table they draw), the
-embedding plots ``lda_embeddings.npz`` (the points they scatter), the
+embedding plots ``lda_embeddings.npz`` and ``tsne_embeddings.npz`` (the points
+they scatter; the t-SNE runs on the device, ``tsne.fit_transform``), the
 confusion-matrix plots ``confusion_matrices.json`` /
 ``region_confusion_matrices.json``.  scikit-learn's ``classification_report``
 and ``confusion_matrix`` are restated here (checked against scikit-learn 1.7.2
 by ``tests/golden/make_evaluate.py``).  Out of scope:
 ``interpolate_syndrome_to_normal``, ``classify_and_project``, the pre- /
-post-operative evaluation, t-SNE, the ``LinearSVC`` and every plot.
+post-operative evaluation, the ``LinearSVC`` and every plot.
 
 Latents are decoded in chunks of exactly ``batch_size ** 2`` rows (the last
 one padded), so a decoded head does not depend on how many others were asked
@@ -32,7 +33,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops, precompute, rendering
+from . import ops, precompute, rendering, tsne
 
 N_STEPS = 10  # frames per latent variable of a traversal (test.py:144)
 
@@ -478,7 +479,8 @@ class Tester:
         ``augmented`` over train then test rows, ``region_keys`` and one
         ``region_<i>`` ``[N_train, 2]`` per region."""
         if mode == "tsne":
-            raise NotImplementedError("t-SNE embeddings are not part of this package")
+            raise NotImplementedError("embeddings() draws the LDA projection and needs classifiers; "
+                                      "the t-SNE embedding is tsne_embeddings()")
         if mode != "lda":
             raise NotImplementedError(f"embedding mode {mode!r}")
         self._need_classifiers()
@@ -498,6 +500,26 @@ class Tester:
             out[f"region_{i}"] = e.cpu().numpy()
         path = self._path("lda_embeddings.npz")
         np.savez(path, **out)
+        return path
+
+    def tsne_embeddings(self, perplexity=30.0, generator=None):
+        """The points of ``plot_embeddings``'s other branch (``test.py:1177-1180``:
+        ``TSNE(n_components=2, init='random')`` of the train and test
+        latents), embedded on the device by :func:`tsne.fit_transform`; no
+        classifiers are needed.  Writes ``tsne_embeddings.npz``: ``x1``,
+        ``x2``, ``class``, ``is_test``, ``augmented`` over train then test rows
+        (the rows of ``lda_embeddings.npz``), ``kl_divergence``, ``n_iter`` and
+        ``perplexity``.  ``generator``: the CPU ``torch.Generator`` of the
+        random initial embedding."""
+        tr_z, tr_l, tr_a = self._latents_and_labels(self._train_set)
+        ts_z, ts_l, ts_a = self._latents_and_labels(self._test_set)
+        fit = tsne.fit_transform(torch.cat([tr_z, ts_z]).contiguous(), perplexity=perplexity, generator=generator)
+        xy = fit.y.cpu().numpy()
+        path = self._path("tsne_embeddings.npz")
+        np.savez(path, x1=xy[:, 0], x2=xy[:, 1], **{"class": np.array(tr_l + ts_l)},
+                 is_test=np.array([False] * len(tr_l) + [True] * len(ts_l)), augmented=np.concatenate([tr_a, ts_a]),
+                 kl_divergence=np.float64(fit.kl_divergence), n_iter=np.int64(fit.n_iter),
+                 perplexity=np.float64(perplexity))
         return path
 
     def test_classifiers(self):
@@ -556,11 +578,12 @@ class Tester:
         _dump(self._path("eval_metrics.json"), out)
         return out
 
-    STEPS = ("traversals", "embeddings", "classifiers", "generation", "metrics", "interpolate")
+    STEPS = ("traversals", "embeddings", "classifiers", "generation", "metrics", "interpolate", "tsne")
 
     def run(self, step):
-        """One step of the evaluation by name (``STEPS``); ``interpolate`` is
-        not part of :meth:`__call__`, as in the reference."""
+        """One step of the evaluation by name (``STEPS``); ``interpolate`` and
+        ``tsne`` are not part of :meth:`__call__`, as in the reference (whose
+        ``__call__`` draws the LDA embedding only)."""
         if step == "traversals":
             return self.latent_traversals(use_z_stats=False, animations=self.animations)
         if step == "embeddings":
@@ -574,6 +597,8 @@ class Tester:
             return self.metrics()
         if step == "interpolate":
             return self.interpolate(animations=self.animations)
+        if step == "tsne":
+            return self.tsne_embeddings(generator=self._generator(5))
         raise ValueError(f"unknown step {step!r}; expected one of {self.STEPS}")
 
     def __call__(self):

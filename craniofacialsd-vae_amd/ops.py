@@ -2040,3 +2040,173 @@ def spmm_x(csr, x, m, elu_y=None, out=None, order=None, uniform=0, sched=None):
     call("cfsd_spmm_csr_x", ptr(row_ptr), ptr(col), ptr(val), ptr(x), _st(x), ptr(elu_y), ptr(out),
          _st(out), bsz, m, n, c, stream_ptr())
     return out
+
+
+# ------------------------------------------------------------------ t-SNE
+TSNE_MAX_K, TSNE_MAX_D = _H["CFSD_TSNE_MAX_K"], _H["CFSD_TSNE_MAX_D"]
+TSNE_KNN_ROWS, TSNE_KNN_COLS, TSNE_KNN_DIMS = (_H["CFSD_TSNE_KNN_ROWS"], _H["CFSD_TSNE_KNN_COLS"],
+                                               _H["CFSD_TSNE_KNN_DIMS"])  # cfsd_knn_rows' tiling
+TSNE_ROWS, TSNE_TILE = _H["CFSD_TSNE_ROWS"], _H["CFSD_TSNE_TILE"]  # the repulsive kernel's rows / staged columns
+TSNE_MAX_SPLITS, TSNE_MAX_N = _H["CFSD_TSNE_MAX_SPLITS"], _H["CFSD_TSNE_MAX_N"]
+TSNE_LONG_ROW, TSNE_ATT_ROWS = _H["CFSD_TSNE_LONG_ROW"], _H["CFSD_TSNE_ATT_ROWS"]  # the attractive kernel's
+
+
+def _knn_limits(n, k, what):
+    if n < 2:
+        raise ValueError(f"{what}: {n} rows, at least 2")
+    if not 1 <= k <= min(n - 1, TSNE_MAX_K):
+        raise ValueError(f"{what}: k={k} outside 1..min(n - 1 = {n - 1}, {TSNE_MAX_K})")
+    if n * k >= 2 ** 31:
+        raise ValueError(f"{what}: n x k = {n * k} >= 2^31")
+
+
+def knn_rows(z, k):
+    """The ``k`` nearest other rows of every row of ``z`` ``[n, d]``
+    (``cfsd_knn_rows``): ``(idx [n, k] int32, d2 [n, k] float32)``, squared
+    Euclidean distances in difference form, each row sorted ascending by
+    ``(d2, index)``; the row itself is excluded."""
+    _need(z, None, name="z")
+    if z.dim() != 2:
+        raise ValueError(f"z: shape {tuple(z.shape)}, expected [n, d]")
+    n, d, k = int(z.shape[0]), int(z.shape[1]), int(k)
+    _knn_limits(n, k, "knn_rows")
+    if not 1 <= d <= TSNE_MAX_D:
+        raise ValueError(f"knn_rows: d={d} outside 1..{TSNE_MAX_D}")
+    idx = torch.empty((n, k), dtype=torch.int32, device=z.device)
+    d2 = torch.empty((n, k), dtype=torch.float32, device=z.device)
+    call("cfsd_knn_rows", ptr(z), ptr(idx), ptr(d2), None, ctypes.c_size_t(0), n, d, k, stream_ptr())
+    return idx, d2
+
+
+def tsne_affinities(d2, perplexity):
+    """``_binary_search_perplexity`` (``sklearn/manifold/_utils.pyx``) on the
+    device, in float64 (``cfsd_tsne_affinities``): ``d2`` ``[n, k]`` squared
+    neighbour distances -> ``(p_cond [n, k], beta [n])`` float32, the
+    conditional probabilities of the last precision the search evaluated and
+    that precision."""
+    _need(d2, None, name="d2")
+    if d2.dim() != 2:
+        raise ValueError(f"d2: shape {tuple(d2.shape)}, expected [n, k]")
+    n, k = int(d2.shape[0]), int(d2.shape[1])
+    _knn_limits(n, k, "tsne_affinities")
+    perplexity = float(perplexity)
+    if not 0.0 < perplexity < float("inf"):
+        raise ValueError(f"perplexity {perplexity} is not a positive number")
+    p_cond = torch.empty((n, k), dtype=torch.float32, device=d2.device)
+    beta = torch.empty((n,), dtype=torch.float32, device=d2.device)
+    call("cfsd_tsne_affinities", ptr(d2), ptr(p_cond), ptr(beta), n, k, perplexity, stream_ptr())
+    return p_cond, beta
+
+
+def tsne_symmetrize(idx, p_cond):
+    """The second half of ``_joint_probabilities_nn`` (``sklearn/manifold/_t_sne.py``):
+    ``P = (P_cond + P_cond^T) / sum`` of the kNN-sparse conditional
+    probabilities ``idx`` / ``p_cond`` ``[n, k]``, as a CSR ``(row_ptr [n + 1]
+    int32, col [nnz] int32 ascending within a row, val [nnz] float32)``.
+    Float64 on the tensors' own device (CPU tensors are fine: torch only, no
+    kernel); an entry is the sum of at most two terms, so no order is left
+    open.  Entries that are exactly 0 are dropped, as scipy's sparse addition
+    drops them."""
+    if idx.dim() != 2 or idx.shape != p_cond.shape or idx.device != p_cond.device:
+        raise ValueError(f"idx {tuple(idx.shape)} and p_cond {tuple(p_cond.shape)}: expected two [n, k] on one device")
+    n, k = int(idx.shape[0]), int(idx.shape[1])
+    rows = torch.arange(n, device=idx.device, dtype=torch.int64).repeat_interleave(k)
+    cols = idx.reshape(-1).to(torch.int64)
+    if n < 2 or k < 1 or int(cols.min()) < 0 or int(cols.max()) >= n:
+        raise ValueError("tsne_symmetrize: neighbour indices outside [0, n)")
+    vals = p_cond.reshape(-1).to(torch.float64)
+    keys, order = torch.sort(torch.cat([rows * n + cols, cols * n + rows]), stable=True)
+    vals = torch.cat([vals, vals])[order]
+    first = torch.ones_like(keys, dtype=torch.bool)
+    first[1:] = keys[1:] != keys[:-1]
+    if int((~first[1:] & ~first[:-1]).sum()) != 0:
+        raise ValueError("tsne_symmetrize: a row names one neighbour twice")
+    twin = torch.zeros_like(vals)  # the transposed entry, where there is one, follows its key directly
+    twin[:-1] = torch.where(first[1:], twin[:-1], vals[1:])
+    keep = first & ((vals + twin) != 0)
+    keys, val = keys[keep], (vals + twin)[keep]
+    if keys.numel() >= 2 ** 31:
+        raise ValueError(f"tsne_symmetrize: nnz = {keys.numel()} >= 2^31")
+    total = torch.clamp(val.sum(), min=torch.finfo(torch.float64).eps)
+    row_ptr = torch.searchsorted(keys, torch.arange(n + 1, device=keys.device, dtype=torch.int64) * n)
+    return row_ptr.to(torch.int32), (keys % n).to(torch.int32), (val / total).to(torch.float32)
+
+
+def tsne_joint_probabilities(z, perplexity=30.0):
+    """``_joint_probabilities_nn`` of ``TSNE(method='barnes_hut')``: the
+    ``k = min(n - 1, int(3 * perplexity + 1))`` nearest neighbours of every
+    row of ``z`` ``[n, d]`` (:func:`knn_rows`), the perplexity search
+    (:func:`tsne_affinities`) and the symmetrisation (:func:`tsne_symmetrize`)
+    -> the CSR ``(row_ptr, col, val)`` of ``P``.  ``perplexity >= n`` is a
+    ``ValueError``, as in scikit-learn."""
+    if z is None or z.dim() != 2:
+        raise ValueError("z: expected a tensor [n, d]")
+    n, perplexity = int(z.shape[0]), float(perplexity)
+    if not perplexity > 0.0:
+        raise ValueError(f"perplexity {perplexity} is not a positive number")
+    if perplexity >= n:
+        raise ValueError("perplexity must be less than n_samples")
+    _need(z, None, name="z")
+    idx, d2 = knn_rows(z, min(n - 1, int(3.0 * perplexity + 1)))
+    p_cond, _ = tsne_affinities(d2, perplexity)
+    return tsne_symmetrize(idx, p_cond)
+
+
+def tsne_splits(n):
+    """``cfsd_tsne_splits``: the column splits per row block that ``splits=0``
+    stands for; a function of ``n`` alone."""
+    return int(_abi.lib().cfsd_tsne_splits(int(n)))
+
+
+def tsne_workspace(n, splits=0, device="cuda"):
+    """Scratch of one :func:`tsne_step` (``cfsd_tsne_step_workspace``)."""
+    need = int(_abi.lib().cfsd_tsne_step_workspace(int(n), int(splits)))
+    if need == 0:
+        raise ValueError(f"tsne_workspace: n={n} or splits={splits} outside the supported range")
+    return torch.empty(need // 4 + 1, dtype=torch.float32, device=device)
+
+
+def tsne_step(y, update, gains, csr, momentum, learning_rate, exaggeration=1.0, splits=0, want_error=False,
+              workspace=None, grad=None, result=None):
+    """One iteration of ``_gradient_descent`` on ``_kl_divergence_bh(angle=0)``
+    (``sklearn/manifold/_t_sne.py``), three launches and no synchronisation:
+    the exact repulsive term, the attractive term over the CSR ``csr =
+    (row_ptr, col, val)`` of ``P`` (times ``exaggeration``), ``grad = 4 (attr -
+    rep / Z)`` and the gains / momentum rule, which updates ``y``, ``update``
+    and ``gains`` ``[n, 2]`` IN PLACE.  ``splits``: column splits of the
+    repulsive kernel (0 = :func:`tsne_splits`).  Returns ``grad`` ``[n, 2]``;
+    with ``want_error`` ``(grad, result)``, ``result`` two device floats: the
+    KL divergence and ``|gains * grad|`` as ``_gradient_descent`` checks them."""
+    _need(y, None, name="y")
+    if y.dim() != 2 or y.shape[1] != 2:
+        raise ValueError(f"y: shape {tuple(y.shape)}, expected [n, 2]")
+    n = int(y.shape[0])
+    if not 2 <= n <= TSNE_MAX_N:
+        raise ValueError(f"tsne_step: n={n} outside 2..{TSNE_MAX_N}")
+    _need(update, (n, 2), name="update")
+    _need(gains, (n, 2), name="gains")
+    row_ptr, col, val = csr
+    _need(row_ptr, (n + 1,), torch.int32, "row_ptr")
+    _need(col, None, torch.int32, "col")
+    nnz = int(col.numel())
+    _need(col, (nnz,), torch.int32, "col")
+    _need(val, (nnz,), name="val")
+    splits = int(splits)
+    if not 0 <= splits <= TSNE_MAX_SPLITS:
+        raise ValueError(f"tsne_step: splits={splits} outside 0..{TSNE_MAX_SPLITS}")
+    if not float(exaggeration) > 0.0:
+        raise ValueError(f"tsne_step: exaggeration {exaggeration} <= 0")
+    if workspace is None:
+        workspace = tsne_workspace(n, splits, y.device)
+    _need(workspace, None, name="workspace")
+    nbytes = ctypes.c_size_t(workspace.numel() * workspace.element_size())
+    grad = _out(grad, (n, 2), y, "grad")
+    want = 1 if want_error else 0
+    if want_error:
+        result = _out(result, (2,), y, "result")
+    call("cfsd_tsne_forces", ptr(y), ptr(row_ptr), ptr(col), ptr(val), ptr(workspace), nbytes, n, nnz, splits,
+         float(exaggeration), want, stream_ptr())
+    call("cfsd_tsne_update", ptr(y), ptr(update), ptr(gains), ptr(grad), ptr(result) if want_error else None,
+         ptr(workspace), nbytes, n, splits, float(exaggeration), float(momentum), float(learning_rate), want,
+         stream_ptr())
+    return (grad, result) if want_error else grad

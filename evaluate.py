@@ -7,7 +7,9 @@ per-region table, random generation, reconstruction errors and the two
 diversity figures (``eval_metrics.json``) and, when the run trained
 classifiers, their test reports.  Everything is written into
 ``<output_path>/outputs/<ID>``.  ``--only`` runs single steps: traversals,
-embeddings, classifiers, generation, metrics, interpolate."""
+embeddings, classifiers, generation, metrics, interpolate, tsne (the t-SNE
+embedding of the train and test latents, ``tsne_embeddings.npz``; it needs no
+classifiers and is not part of the whole run, as in the reference)."""
 import os
 import sys
 

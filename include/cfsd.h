@@ -992,6 +992,110 @@ int cfsd_mlp_head_step(const float* z, int ld_z, int row_stride, const int32_t* 
                        int bs, int train, float lr, float beta1, float beta2, float eps, float weight_decay,
                        void* stream);
 
+/* ---------------------------------------------------------------- t-SNE
+ * The t-SNE branch of Tester.plot_embeddings (test.py:1177-1180:
+ * sklearn.manifold.TSNE(n_components=2, init='random')), ABI 4.21:
+ * scikit-learn 1.7.2's method='barnes_hut' at angle = 0, i.e. kNN-sparse input
+ * affinities, the EXACT repulsive term, degrees_of_freedom = 1.  No atomics:
+ * every sum below has one order fixed by the sizes, two calls give the same
+ * bits.  Every entry point checks its arguments before any HIP call.
+ *
+ * cfsd_knn_rows: z [n, d] fp32 -> idx [n, k] int32, d2 [n, k] fp32: per row
+ * the k nearest OTHER rows under
+ *   d2(i, j) = acc_d,  acc_0 = +0,  acc_{c+1} = fma(t_c, t_c, fma(2 e_c, t_c, acc_c)),
+ *   t_c = fl(z[i,c] - z[j,c]),  e_c = (z[i,c] - z[j,c]) - t_c  (exact: Knuth's TwoSum in fp32)
+ * (all fp32, ascending c, nothing else fused; never |a|^2 + |b|^2 - 2ab).  The
+ * sum is rounded twice per coordinate and e_c^2 is dropped: d2 is within
+ * d * 2^-23 relative of the exact distance, and exact whenever every difference
+ * and partial sum is representable (small integers).  Sorted ascending by
+ * (d2, j): equal distances go to the lower index.  The candidates of a row
+ * are walked in ascending j, CFSD_TSNE_KNN_COLS per tile and
+ * CFSD_TSNE_KNN_DIMS coordinates per staged chunk, CFSD_TSNE_KNN_ROWS query
+ * rows per workgroup; the selection is a sorted insertion per row and depends
+ * on none of the three.  Limits (CFSD_EINVAL): 2 <= n, 1 <= k <= min(n - 1,
+ * CFSD_TSNE_MAX_K), 1 <= d <= CFSD_TSNE_MAX_D, n * k < 2^31.  A NaN
+ * coordinate makes its distances NaN, which sort after every number.
+ * workspace: cfsd_knn_rows_workspace() bytes -- 0 in this version (a row's k
+ * best live in LDS), NULL allowed.
+ *
+ * cfsd_tsne_affinities: _binary_search_perplexity (sklearn/manifold/_utils.pyx)
+ * per row of d2 [n, k]: beta = 1 with unbounded brackets, doubled / halved
+ * while unbounded and bisected after, at most 100 evaluations, stopping at
+ * |H - log(perplexity)| <= 1e-5 with H = log(sum) + beta * sum_j d2_j P_j,
+ * P_j = exp(-beta d2_j) / sum, and sum == 0 replaced by 1e-8 (both constants
+ * are C floats there and here).  All of it in float64; a row's sums are
+ * formed by one wave (lane l adds j = l, l + 64, ..., then a fixed butterfly).
+ * p_cond [n, k] = P of the LAST evaluated beta and beta [n] = that beta, both
+ * rounded to fp32.  Limits: those of cfsd_knn_rows on n and k; perplexity a
+ * positive finite number.
+ *
+ * One gradient-descent step = cfsd_tsne_forces (two launches) then
+ * cfsd_tsne_update (one), no host synchronisation.  y, update, gains, grad
+ * [n, 2] fp32; P a symmetric CSR: row_ptr [n + 1] int32, col [nnz] int32
+ * (ascending within a row, clamped into [0, n)), val [nnz] fp32.
+ * With q_ij = 1 / (1 + |y_i - y_j|^2) (fp32, the hardware reciprocal):
+ *   rep_i  = sum_{j != i} q_ij^2 (y_i - y_j),  zrow_i = sum_{j != i} q_ij
+ *     over ALL j != i (a distinct point at the same position counts, q = 1).
+ *     Workgroups of CFSD_TSNE_ROWS rows x `splits` column ranges; a range is
+ *     ceil(tiles / splits) tiles of CFSD_TSNE_TILE columns.  Per row: a tile's
+ *     columns are added in ascending j onto +0, the tile sums in ascending
+ *     order onto the split's, the splits' in ascending order (fp32).
+ *     splits = 0 means cfsd_tsne_splits(n), a function of n alone;
+ *     1 <= splits <= CFSD_TSNE_MAX_SPLITS otherwise.  Different split counts
+ *     group the same terms differently (fp32 rounding only).
+ *   attr_i = exaggeration * sum_j val_ij q_ij (y_i - y_j) over row i.  A row of
+ *     at most CFSD_TSNE_LONG_ROW entries: lane l of one wave adds the entries
+ *     l, l + 64, ... in ascending order, then the butterfly.  A longer row:
+ *     thread t of 1024 adds t, t + 1024, ..., each wave's butterfly, the 16
+ *     wave sums in ascending order.  CFSD_TSNE_ATT_ROWS rows per workgroup.
+ *   Z = max(sum_i zrow_i, DBL_EPSILON) in float64: per attraction workgroup
+ *     its rows in ascending order, then thread t of 1024 adds the workgroup
+ *     sums t, t + 1024, ..., then a halving tree.
+ *   grad_i = 4 (attr_i - rep_i * (float)(1 / Z))
+ *   _gradient_descent's rule per coordinate, fp32, nothing fused:
+ *     gains = max(update * grad < 0 ? gains + 0.2 : gains * 0.8, 0.01)
+ *     update = momentum * update - learning_rate * (gains * grad);  y += update
+ * want_error != 0 (pass the same flag to both calls) also writes result[0..1]:
+ *   result[0] = KL = a * (sum_ij p_ij log(p_ij / q_ij) + (sum p) (log a + log Z)),
+ *     a = exaggeration, i.e. the divergence of a P against q / Z as
+ *     _gradient_descent reports it; float64 throughout, -log q_ij evaluated
+ *     as log1p(|y_i - y_j|^2).  At the extremes where scikit-learn clamps p
+ *     and q / Z at float64 eps inside the logarithm: an entry p_ij <= 0
+ *     contributes 0 (the limit of p log p), log1p is finite for every finite
+ *     fp32 y, and Z >= DBL_EPSILON -- so KL is finite whenever y and val are.
+ *   result[1] = |gains * grad|_2 over all 2n coordinates, the norm
+ *     _gradient_descent compares with min_grad_norm (after its in-place
+ *     grad *= gains); float64 sum, fixed order.
+ *   The update then runs as ONE workgroup; y, update, gains and grad carry the
+ *   same bits with and without the flag.
+ * workspace: cfsd_tsne_step_workspace(n, splits) bytes (0 for invalid sizes),
+ * 16-byte aligned, the same buffer and `splits` for both calls.
+ * Limits: 2 <= n <= CFSD_TSNE_MAX_N, nnz >= 0, exaggeration > 0. */
+#define CFSD_TSNE_MAX_K 256
+#define CFSD_TSNE_MAX_D 512
+#define CFSD_TSNE_MAX_N 16777216
+#define CFSD_TSNE_KNN_ROWS 16
+#define CFSD_TSNE_KNN_COLS 64
+#define CFSD_TSNE_KNN_DIMS 64
+#define CFSD_TSNE_ROWS 512
+#define CFSD_TSNE_TILE 128
+#define CFSD_TSNE_MAX_SPLITS 64
+#define CFSD_TSNE_LONG_ROW 256
+#define CFSD_TSNE_ATT_ROWS 16
+size_t cfsd_knn_rows_workspace(int n, int d, int k);
+int cfsd_knn_rows(const float* z, int32_t* idx, float* d2, void* workspace, size_t workspace_bytes, int n, int d,
+                  int k, void* stream);
+int cfsd_tsne_affinities(const float* d2, float* p_cond, float* beta, int n, int k, float perplexity,
+                         void* stream);
+int cfsd_tsne_splits(int n);
+size_t cfsd_tsne_step_workspace(int n, int splits);
+int cfsd_tsne_forces(const float* y, const int32_t* row_ptr, const int32_t* col, const float* val,
+                     void* workspace, size_t workspace_bytes, int n, int nnz, int splits, float exaggeration,
+                     int want_error, void* stream);
+int cfsd_tsne_update(float* y, float* update, float* gains, float* grad, float* result, const void* workspace,
+                     size_t workspace_bytes, int n, int splits, float exaggeration, float momentum,
+                     float learning_rate, int want_error, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
