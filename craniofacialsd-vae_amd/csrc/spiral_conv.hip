@@ -3464,17 +3464,19 @@ extern "C" int cfsd_spiral_conv_bwd_weight_x(const void* x, int x_dt, const int3
     return rc;
   if (!workspace) return set_error(CFSD_EINVAL, "null workspace");
   if ((rc = check_dw_db(dw, db))) return rc;
-  if ((rc = check_workspace(workspace_bytes, cfsd_spiral_conv_bwd_weight_x_workspace(batch, rows, seq, cin, cout))))
-    return rc;
   const hipStream_t st = (hipStream_t)stream;
   const int xvm = vm_of(x_dt), dpvm = vm_of(dpre_dt);
   const DwXRoute r = dw_x_route(x_dt, dpre_dt, batch, cin, cout);
   if (r.kind == kDwXNone)
     return set_error(CFSD_EINVAL, "spiral_conv_bwd_weight_x: unsupported %d -> %d with dtypes %d/%d (fp32 x: fp32 dpre)",
                      cin, cout, x_dt, dpre_dt);
+  // an fp32 x runs the fp32 kernels on THEIR slab set (cfsd_spiral_conv_bwd_weight_workspace, checked by
+  // dw_f32): the bf16 kernels' set is the larger one just below kLatDwMax rows and must not be asked of it
   if (r.kind == kDwXF32)
     return dw_f32(r.code, (const float*)x, xvm, idx, (const float*)dpre, dpvm, dw, db, workspace, workspace_bytes,
                   batch, vsrc, rows, cin, cout, st);
+  if ((rc = check_workspace(workspace_bytes, cfsd_spiral_conv_bwd_weight_x_workspace(batch, rows, seq, cin, cout))))
+    return rc;
   const SlabSet slabs = slab_set(r.code, batch, vsrc, rows, cin, cout);
   if (r.kind == kDwXBf16) {
     rc = bf::launch_dw((const bf16_t*)x, xvm, idx, dpre, dpre_dt, workspace, vsrc, rows, (long)batch * rows, cin,

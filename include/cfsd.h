@@ -646,7 +646,9 @@ int cfsd_spiral_conv_bwd_data_flat(const void* dpre, int dpre_dt, const int32_t*
  * fp32, each batch-major or vertex-major) and the xyz input layer (x fp32,
  * dpre bf16 or fp32).  dw == db == NULL defers the reduction: the
  * cfsd_dw_reduce_batch item's `fused` is what cfsd_spiral_conv_bwd_weight_x_slabs
- * returns for the same operands. */
+ * returns for the same operands.  Workspace: cfsd_spiral_conv_bwd_weight_x_workspace
+ * for a bf16 x, cfsd_spiral_conv_bwd_weight_workspace (the fp32 kernels' slab
+ * set) for an fp32 x. */
 size_t cfsd_spiral_conv_bwd_weight_x_workspace(int batch, int rows, int seq, int cin, int cout);
 int cfsd_spiral_conv_bwd_weight_x(const void* x, int x_dt, const int32_t* idx, const void* dpre,
                                   int dpre_dt, float* dw, float* db, float* workspace,

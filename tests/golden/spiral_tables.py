@@ -190,7 +190,9 @@ def one_vertex_rows(rows, vsrc, seed=0, every=7):
 def fan_table(rows, vsrc, fan, seed=0):
     """A table whose largest per-vertex fan-in is EXACTLY ``fan`` (the width
     class of ``topology.inverse_flat``: widths 4, 8, 12, 16, and none from 17
-    on).  Four neighbouring vertices in the middle get fan, fan - 1, fan - 2
+    on by default; the full-table entry points take width 20 through
+    ``inverse_flat(..., max_width=20)``, and fan 17 .. 20 builds as well:
+    ``tests/test_exact_values_host.py``).  Four neighbouring vertices in the middle get fan, fan - 1, fan - 2
     and fan - 3 positions (every padding of the last int4 group of a flat-list
     row), the vertices of ``gap_vertices`` none, a tenth of the rest a uniform
     draw from 0 .. fan (as far as the positions last) and the others an even

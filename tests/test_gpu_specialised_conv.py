@@ -111,7 +111,8 @@ Not covered, with the reason:
   * conv_bwd_lat_pair<64,32,1> (LatPairShapes x LatPairCtws): dx_lat_ctw(64, 32) is the constant 2.
   * conv_dw_in_small<3,32>, <3,64> (InSmallShapes): dw_geom gives cin <= 3, cout 32 / 64 to conv_dw_in_mfma.
   * conv_fwd_out_small<32,1>, <32,2> (OutSmallShapes): taken by cfsd_spiral_conv_fwd_x alone (out of scope).
-  * the bf16 and vertex-major entry points: they need a rounding model of their own.
+  * the bf16 and vertex-major entry points: ``test_gpu_vertex_major_conv`` and ``test_gpu_bf16_conv`` (exact-value
+    inputs and a rounding model of their own).
 """
 import ctypes
 
