@@ -577,3 +577,15 @@ class ClassifierStage:
         self._need_classifiers()
         qda = self.qda if region == "all" else self.region_qdas[region]
         return torch.sqrt(qda.mahalanobis2(z)[:, qda.class_position(self.class2idx(distribution_class))])
+
+    def qda_gaussian(self, distribution_class="n", region="all"):
+        """``(mean [d], whiten [d, d], cols)`` of the QDA Gaussian of
+        ``distribution_class``, of the whole latent or of one latent region:
+        the fp32 device tensors the scores are computed from and the column
+        window ``(col0, d)`` they apply to (``None``: every column).  What the
+        planning kernels (``ops.plan_targets``, ``ops.pair_metrics``) read."""
+        self._need_classifiers()
+        qda = self.qda if region == "all" else self.region_qdas[region]
+        qda._fitted()
+        pos = qda.class_position(self.class2idx(distribution_class))
+        return qda._mean[pos].contiguous(), qda._whiten[pos].contiguous(), qda.cols

@@ -18,9 +18,16 @@ they scatter; the t-SNE runs on the device, ``tsne.fit_transform``), the
 confusion-matrix plots ``confusion_matrices.json`` /
 ``region_confusion_matrices.json``.  scikit-learn's ``classification_report``
 and ``confusion_matrix`` are restated here (checked against scikit-learn 1.7.2
-by ``tests/golden/make_evaluate.py``).  Out of scope:
-``interpolate_syndrome_to_normal``, ``classify_and_project``, the pre- /
-post-operative evaluation, the ``LinearSVC`` and every plot.
+by ``tests/golden/make_evaluate.py``).
+
+Surgical planning (``interpolate_syndrome_to_normal``, ``classify_and_project``,
+the pre- / post-operative metrics) runs on three kernels of
+``csrc/planning.hip``: the crossings of a patient's path to the healthy
+distribution in closed form (``ops.plan_targets``), the latent tables of the
+planned procedures (``ops.plan_tables``) and the raw quantities of every pair
+and region in one launch (``ops.pair_metrics``).  The figures the reference
+draws its points into become JSON files of those points.  Out of scope: the
+``LinearSVC`` and every plot.
 
 Latents are decoded in chunks of exactly ``batch_size ** 2`` rows (the last
 one padded), so a decoded head does not depend on how many others were asked
@@ -119,6 +126,93 @@ def _dump(path, obj):
     with open(path, "w") as f:
         json.dump(obj, f)
     return path
+
+
+# ---------------------------------------------------------------- surgical planning, host side
+PLAN_LEVELS = (3.0, 2.0, 1.0)  # the shells of the healthy distribution a path is cut at (test.py:681-684)
+PLAN_STEPS = 5000              # points of the path the crossings are searched on (test.py:693)
+PLAN_FIRST = 8                 # frames from the patient to the first shell (test.py:706)
+PAIR_COLUMNS = ("PID", "Pre name", "Post name", "Surgery regions", "Procedure", "Syndrome")
+
+
+def planning_procedures(config, latent_regions):
+    """The procedures of a run: ``planning: procedures: {name: [region key,
+    ...]}`` of its configuration, validated against ``latent_regions`` (the
+    reference keeps its own table in ``utils.py``); without the section one
+    procedure per region, named by the region's key.  Returns ``{name: [region
+    keys as they are in latent_regions]}`` in the configuration's order."""
+    by_name = {str(k): k for k in latent_regions}
+    section = (config.get("planning") or {}).get("procedures")
+    if section is None:
+        return {name: [key] for name, key in by_name.items()}
+    if not isinstance(section, dict) or not section:
+        raise ValueError("planning.procedures: expected a mapping {procedure name: [region key, ...]}")
+    out = {}
+    for name, keys in section.items():
+        name = str(name)
+        if not name or os.sep in name or name in (".", "..", "all_attributes"):
+            raise ValueError(f"planning.procedures: {name!r} cannot name a procedure (it names its folder)")
+        if isinstance(keys, (str, bytes)) or not hasattr(keys, "__iter__"):
+            raise ValueError(f"planning.procedures.{name}: expected a list of region keys, got {keys!r}")
+        keys = [str(k) for k in keys]
+        unknown = [k for k in keys if k not in by_name]
+        if not keys or unknown or len(set(keys)) != len(keys):
+            raise ValueError(f"planning.procedures.{name}: {keys}: expected one or more different keys of "
+                             f"{sorted(by_name)}" + (f"; unknown {unknown}" if unknown else ""))
+        out[name] = [by_name[k] for k in keys]
+    return out
+
+
+def read_pairs_table(path):
+    """The table of ``evaluate_all_pre_post_pairs`` as a pandas frame: a
+    ``.csv`` (``read_csv``) or a spreadsheet (``read_excel``, as
+    ``data.get_dataset_summary``) with the columns ``PAIR_COLUMNS``; ``PID``
+    becomes a string (it names a file), the other cells are stripped strings."""
+    import pandas as pd
+    path = str(path)
+    frame = pd.read_csv(path, dtype=str) if path.endswith(".csv") else pd.read_excel(path, dtype=str)
+    frame.columns = [str(c).strip() for c in frame.columns]
+    missing = [c for c in PAIR_COLUMNS if c not in frame.columns]
+    if missing:
+        raise ValueError(f"{path}: columns {missing} missing; expected {list(PAIR_COLUMNS)}")
+    if not len(frame):
+        raise ValueError(f"{path}: no rows")
+    for c in PAIR_COLUMNS:
+        if frame[c].isna().any():
+            raise ValueError(f"{path}: column {c!r} has empty cells")
+        frame[c] = frame[c].str.strip()
+    if frame["PID"].duplicated().any():
+        raise ValueError(f"{path}: PID {sorted(frame['PID'][frame['PID'].duplicated()])} more than once")
+    return frame
+
+
+def compose_pair_metrics(raw, region_keys, affected, weights=None):
+    """The metrics of ``test.py:992-1088`` from one pair's raw quantities
+    ``raw`` ``[1 + R, 6]`` (``ops.PAIR_RAW``; row 0 the whole latent, row ``1 +
+    r`` region ``region_keys[r]``), in float64: ``global_metric = (d_pre -
+    d_post) / d_post`` on the Mahalanobis distances, ``global_metric_l2`` the
+    same on the Euclidean ones, ``global_metric_directional = |displacement|_M
+    cos / d_post``; per affected region ``metric_distances`` and
+    ``metric_with_angle`` likewise; ``procedure_metric`` the mean over the
+    affected regions of ``w * metric_distances`` (``weights``: region key ->
+    the region QDA's accuracy, 1 without)."""
+    raw = np.asarray(raw, np.float64)
+    if raw.shape != (1 + len(region_keys), 6):
+        raise ValueError(f"raw: shape {raw.shape}, expected {(1 + len(region_keys), 6)}")
+    if not affected:
+        raise ValueError("a procedure affects at least one region")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        distances = (raw[:, 0] - raw[:, 1]) / raw[:, 1]
+        with_angle = raw[:, 5] * raw[:, 4] / raw[:, 1]
+        l2 = (raw[0, 2] - raw[0, 3]) / raw[0, 3]
+    row = {k: 1 + r for r, k in enumerate(region_keys)}
+    procedure = 0.0
+    for k in affected:
+        procedure += (1 if weights is None else float(weights[str(k)])) * distances[row[k]]
+    return {"global_metric": float(distances[0]), "global_metric_l2": float(l2),
+            "global_metric_directional": float(with_angle[0]), "procedure_metric": float(procedure / len(affected)),
+            "region_metrics": {k: {"metric_distances": float(distances[row[k]]),
+                                   "metric_with_angle": float(with_angle[row[k]])} for k in affected}}
 
 
 class Tester:
@@ -564,6 +658,260 @@ class Tester:
         self.classifier_files = files
         return acc
 
+    # ------------------------------------------------------------ surgical planning
+    def _load_and_encode(self, mesh_path):
+        """``test.py:637-650``: the latent ``[1, latent]`` (device) of the mesh
+        file ``mesh_path``, normalised as the training data was."""
+        from .data import load_mesh
+        v = load_mesh(str(mesh_path)).to(self._device, torch.float32)
+        if self._normalized_data:
+            v = (v - self._mean) / self._std
+        return self._manager.encode(v.unsqueeze(0).contiguous()).contiguous()
+
+    @staticmethod
+    def _mesh_id(mesh_path):
+        return os.path.splitext(os.path.basename(str(mesh_path)))[0]
+
+    def _region_projections(self, z):
+        """Per latent region the region LDA's first and last component of the
+        latents ``z`` ``[N, latent]``: ``{str(key): [[x1, x2], ...]}`` (empty
+        without region classifiers)."""
+        m = self._manager
+        if m.region_ldas is None:
+            return {}
+        out = {}
+        for key in m.latent_regions:
+            e = m.region_ldas[key].transform(z)
+            out[str(key)] = torch.stack([e[:, 0], e[:, -1]], dim=1).cpu().tolist()
+        return out
+
+    def plan_to_normal(self, z, levels=PLAN_LEVELS, steps=PLAN_STEPS, n_first=PLAN_FIRST):
+        """The planning arithmetic of ``test.py:663-740`` for the latents ``z``
+        ``[n, latent]`` (device): the crossings of each path to the mean of
+        the main QDA's class ``n`` (``ops.plan_targets``) and the latent tables
+        of moving every region and of each procedure of
+        :func:`planning_procedures` (``ops.plan_tables``).  Returns ``{"maha"
+        [n], "index" [n, S], "targets" [n, S + 1, latent], "tables" [n, 1 + P,
+        n_first + S, latent], "dist" [n, 1 + P, S + 1], "groups"}``, ``groups``
+        naming the 1 + P groups (``all_attributes`` first)."""
+        self._need_classifiers()
+        m = self._manager
+        mean, whiten, _ = m.qda_gaussian("n")
+        z = z.detach().to(self._device, torch.float32).contiguous()
+        maha, index, targets = ops.plan_targets(z, mean, whiten, levels, steps)
+        procedures = planning_procedures(self._config, m.latent_regions)
+        mask = torch.zeros((len(procedures), z.shape[1]), dtype=torch.uint8)
+        for p, keys in enumerate(procedures.values()):
+            for key in keys:
+                lo, hi = m.latent_regions[key]
+                mask[p, lo:hi] = 1
+        tables, dist = ops.plan_tables(z, targets, mask.to(self._device) if len(procedures) else None, n_first)
+        return {"maha": maha, "index": index, "targets": targets, "tables": tables, "dist": dist,
+                "groups": ["all_attributes"] + list(procedures)}
+
+    def interpolate_syndrome_to_normal(self, patient_path, animations=True):
+        """``test.py:652-870``: the patient's latent moved to the healthy
+        distribution, in every region and in the regions of each procedure
+        (:meth:`plan_to_normal`); all ``(1 + P) * F`` latents decoded at once,
+        their distance to their group's first frame from
+        ``ops.group_vertex_errors``, rendered at 512 pixels on white, plain
+        and as an error map over [0, 10] mm.  Per group, under
+        ``interpolations/<id>_<name>/``: ``meshes/<i>.ply`` and
+        ``meshes_colormap/<i>.ply`` (plasma vertex colours),
+        ``<id>_<name>_interpolate.png`` (renderings above error maps, one
+        column per frame, padding 10), ``.apng`` (rendering | error map, 4
+        fps; with ``animations``) and ``embedding.json`` (``lda``: the 2-D LDA
+        projection of the ``F`` latents, ``regions``: each region LDA's, the
+        points the reference scatters into its pickled figures).
+        ``interpolations/<id>_procedure_distances.csv`` lists ``procedure, d3,
+        d2, d1, dm`` per procedure.  Returns the dictionary of
+        :meth:`plan_to_normal` plus ``frames`` ``[(1 + P) * F, V, 3]``,
+        ``errors`` ``[(1 + P) * F, V]`` and ``files``."""
+        m = self._manager
+        pid = self._mesh_id(patient_path)
+        plan = self.plan_to_normal(self._load_and_encode(patient_path))
+        groups = plan["groups"]
+        n_groups, n_frames, latent = plan["tables"].shape[1:]
+        z_all = plan["tables"].view(n_groups * n_frames, latent)
+        frames = self._unnormalize_verts(self._decode(z_all)).contiguous()
+        errors = ops.group_vertex_errors(frames, n_frames, to_mm=m.to_mm_const)
+        colours = (rendering.errors_to_colors(errors, 0, 10) * 255.0 + 0.5).to(torch.uint8)
+        colours = torch.cat([colours, torch.full_like(colours[..., :1], 255)], dim=-1).cpu().numpy()
+        verts = frames.cpu().numpy()
+        lda_xy = m.lda_project_latents_in_2d(z_all)
+        lda_xy = torch.stack([lda_xy[:, 0], lda_xy[:, -1]], dim=1).cpu().tolist()
+        region_xy = self._region_projections(z_all)
+        root = self._path("interpolations")
+        size, background = m.renderings_size, m.renderings_background
+        self.set_renderings_size(512)
+        self.set_rendering_background_color([1, 1, 1])
+        files = {}
+        try:
+            for g, name in enumerate(groups):
+                sl = slice(g * n_frames, (g + 1) * n_frames)
+                save_id = f"{pid}_{name}"
+                out = os.path.join(root, save_id)
+                for sub in ("meshes", "meshes_colormap"):
+                    os.makedirs(os.path.join(out, sub), exist_ok=True)
+                for i in range(n_frames):
+                    precompute.write_ply(os.path.join(out, "meshes", f"{i}.ply"), verts[sl][i], m.template.faces)
+                    precompute.write_ply(os.path.join(out, "meshes_colormap", f"{i}.ply"), verts[sl][i],
+                                         m.template.faces, colours[sl][i])
+                shots = m.render(frames[sl])
+                maps = m.render(frames[sl], errors[sl], error_max_scale=10)
+                grid = rendering.make_grid(torch.cat([shots, maps], dim=-2), padding=10, pad_value=1.0, nrow=n_frames)
+                files[name] = {"picture": rendering.save_png(os.path.join(out, save_id + "_interpolate.png"), grid)}
+                if animations:
+                    files[name]["animation"] = rendering.save_apng(os.path.join(out, save_id + "_interpolate.apng"),
+                                                                   torch.cat([shots, maps], dim=-1), fps=4)
+                files[name]["embedding"] = _dump(os.path.join(out, "embedding.json"), {
+                    "lda": lda_xy[sl], "regions": {k: v[sl] for k, v in region_xy.items()}})
+        finally:
+            m.renderings_size, m.renderings_background = size, background
+        dist = plan["dist"][0].cpu().numpy().astype(np.float64)
+        files["distances"] = os.path.join(root, f"{pid}_procedure_distances.csv")
+        with open(files["distances"], "w") as f:
+            f.write("procedure,d3,d2,d1,dm\n")
+            for g, name in enumerate(groups[1:], start=1):
+                f.write(name + "," + ",".join(repr(float(v)) for v in dist[g]) + "\n")
+        return {**plan, "frames": frames, "errors": errors, "files": files}
+
+    def classify_and_project(self, patient_path):
+        """``test.py:872-904``: the QDA's class of the patient, its 2-D LDA
+        point and each region LDA's point, returned and written to
+        ``interpolations/<id>_emb.json`` (``class``, ``lda``, ``regions``)."""
+        self._need_classifiers()
+        m = self._manager
+        z = self._load_and_encode(patient_path)
+        xy = m.lda_project_latents_in_2d(z)
+        out = {"class": m.classify_latent(z, "qda")[0], "lda": [float(xy[0, 0]), float(xy[0, -1])],
+               "regions": {k: v[0] for k, v in self._region_projections(z).items()}}
+        os.makedirs(self._path("interpolations"), exist_ok=True)
+        _dump(os.path.join(self._path("interpolations"), self._mesh_id(patient_path) + "_emb.json"), out)
+        return out
+
+    def _pair_windows(self):
+        """The windows of ``ops.pair_metrics``: row 0 the whole latent under
+        the main QDA's healthy class, rows ``1..R`` the latent regions under
+        their own QDAs (none without region classifiers).  Returns ``(region
+        keys, windows, packed mean, packed whiten)``."""
+        m = self._manager
+        keys = list(m.latent_regions) if m.region_qdas is not None else []
+        windows, means, whitens, n_mean, n_whiten = [], [], [], 0, 0
+        for key in ["all"] + keys:
+            mean, whiten, cols = m.qda_gaussian("n", region=key)
+            col0, d = (0, mean.shape[0]) if cols is None else cols
+            windows.append((col0, d, n_mean, n_whiten))
+            means.append(mean)
+            whitens.append(whiten.reshape(-1))
+            n_mean, n_whiten = n_mean + d, n_whiten + d * d
+        return keys, windows, torch.cat(means).contiguous(), torch.cat(whitens).contiguous()
+
+    def _region_weights(self):
+        """``classification_report_regions.json`` of :meth:`test_classifiers`:
+        region key -> the region QDA's accuracy, or None (then the procedure
+        metric is not weighted, ``test.py:1024-1032``)."""
+        try:
+            with open(self._path("classification_report_regions.json")) as f:
+                return {k: float(v["accuracy"]) for k, v in json.load(f).items()}
+        except FileNotFoundError:
+            print("procedure specific metric not weighted according to local QDA performance. "
+                  "Test classifiers first!", flush=True)
+            return None
+
+    def pre_post_metrics(self, z_pre, z_post, patient_ids, procedures):
+        """:meth:`evaluate_pre_post_pair` for ``N`` encoded pairs: ONE
+        ``ops.pair_metrics`` call over every pair and window, everything after
+        it float64 on the host.  ``procedures``: per pair a name of
+        :func:`planning_procedures`.  Writes ``pre_post_eval/<pid>.json`` per
+        pair and returns the list of dictionaries (``raw`` ``[1 + R, 6]``
+        among their entries)."""
+        self._need_classifiers()
+        m = self._manager
+        table = planning_procedures(self._config, m.latent_regions)
+        unknown = sorted({str(p) for p in procedures} - set(table))
+        if unknown:
+            raise ValueError(f"procedure(s) {unknown} not among {sorted(table)} (planning.procedures)")
+        keys, windows, mean, whiten = self._pair_windows()
+        if not keys:
+            raise RuntimeError("the pre- / post-operative metrics need the region classifiers "
+                               "(latent_consistency_weight > 0)")
+        z_pre = z_pre.detach().to(self._device, torch.float32).contiguous()
+        z_post = z_post.detach().to(self._device, torch.float32).contiguous()
+        raw = ops.pair_metrics(z_pre, z_post, windows, mean, whiten).cpu().numpy().astype(np.float64)
+        weights = self._region_weights()
+        classes = [m.classify_latent(z, "qda") for z in (z_pre, z_post)]
+        posteriors = [torch.softmax(m.qda.decision_function(z).double(), dim=1).cpu().tolist() for z in (z_pre, z_post)]
+        lda = [m.lda_project_latents_in_2d(z) for z in (z_pre, z_post)]
+        lda = [torch.stack([e[:, 0], e[:, -1]], dim=1).cpu().tolist() for e in lda]
+        os.makedirs(self._path("pre_post_eval"), exist_ok=True)
+        results = []
+        for i, (pid, procedure) in enumerate(zip(patient_ids, procedures)):
+            out = {"pre_class": classes[0][i], "post_class": classes[1][i],
+                   **compose_pair_metrics(raw[i], keys, table[str(procedure)], weights)}
+            out["region_metrics"] = {str(k): v for k, v in out["region_metrics"].items()}
+            out.update(patient_id=str(pid), procedure=str(procedure), pre_posteriors=posteriors[0][i],
+                       post_posteriors=posteriors[1][i], pre_lda=lda[0][i], post_lda=lda[1][i], raw=raw[i].tolist())
+            _dump(os.path.join(self._path("pre_post_eval"), f"{pid}.json"), out)
+            results.append(out)
+        return results
+
+    def evaluate_pre_post_pair(self, pre_path, post_path, patient_id, procedure):
+        """``test.py:972-1088``: the surgical-effectiveness metrics of one
+        pre- / post-operative pair of mesh files for ``procedure`` (a name of
+        :func:`planning_procedures`).  Returns the reference's dictionary
+        (``pre_class``, ``post_class``, ``global_metric``,
+        ``global_metric_l2``, ``global_metric_directional``,
+        ``procedure_metric``, ``region_metrics``) with the QDA posteriors
+        (``softmax`` of ``decision_function``), the 2-D LDA projections of
+        both latents and the raw quantities, and writes it to
+        ``pre_post_eval/<patient_id>.json``."""
+        return self.pre_post_metrics(self._load_and_encode(pre_path), self._load_and_encode(post_path),
+                                     [patient_id], [procedure])[0]
+
+    def evaluate_all_pre_post_pairs(self, pairs_root, pairs_table):
+        """``test.py:906-970`` without the plots: every row of ``pairs_table``
+        (:func:`read_pairs_table`; ``Surgery regions`` names the procedure)
+        encoded from ``pairs_root`` and evaluated in one
+        :meth:`pre_post_metrics` call.  Writes
+        ``pre_post_eval/<table>_with_results.csv`` (the table plus the scalar
+        metrics) and ``pre_post_eval/region_metrics.json`` (per row
+        ``Procedure``, ``Syndrome`` and the two per-region metrics: the
+        numbers behind the reference's three box plots).  Returns the list of
+        per-pair dictionaries."""
+        frame = read_pairs_table(pairs_table)
+        z_pre = torch.cat([self._load_and_encode(os.path.join(str(pairs_root), n)) for n in frame["Pre name"]])
+        z_post = torch.cat([self._load_and_encode(os.path.join(str(pairs_root), n)) for n in frame["Post name"]])
+        results = self.pre_post_metrics(z_pre, z_post, list(frame["PID"]), list(frame["Surgery regions"]))
+        scalars = ("pre_class", "post_class", "global_metric", "global_metric_l2", "global_metric_directional",
+                   "procedure_metric")
+        for k in scalars:
+            frame[k] = [r[k] for r in results]
+        stem = os.path.splitext(os.path.basename(str(pairs_table)))[0]
+        frame.to_csv(os.path.join(self._path("pre_post_eval"), stem + "_with_results.csv"), index=False)
+        rows = [{"PID": r["patient_id"], "Procedure": proc, "Syndrome": syn,
+                 "metric_distances": {k: v["metric_distances"] for k, v in r["region_metrics"].items()},
+                 "metric_with_angle": {k: v["metric_with_angle"] for k, v in r["region_metrics"].items()}}
+                for r, proc, syn in zip(results, frame["Procedure"], frame["Syndrome"])]
+        _dump(os.path.join(self._path("pre_post_eval"), "region_metrics.json"), {"rows": rows})
+        return results
+
+    def save_postop_colourmap(self, pre_path, post_path):
+        """``compute_and_save_postop_mesh_colourmap`` (``test.py:1138-1151``):
+        the post-operative mesh coloured by its per-vertex distance to the
+        pre-operative one (``ops.vertex_errors``, plasma over [0, 10] mm),
+        written next to it as ``<post>_colmap.ply``."""
+        from .data import load_mesh
+        m = self._manager
+        pre = load_mesh(str(pre_path)).to(self._device).unsqueeze(0).contiguous()
+        post = load_mesh(str(post_path)).to(self._device).unsqueeze(0).contiguous()
+        dist = ops.vertex_errors(post, pre, to_mm=m.to_mm_const)
+        colours = (rendering.errors_to_colors(dist[0], 0, 10) * 255.0 + 0.5).to(torch.uint8)
+        colours = torch.cat([colours, torch.full_like(colours[:, :1], 255)], dim=-1).cpu().numpy()
+        path = os.path.splitext(str(post_path))[0] + "_colmap.ply"
+        precompute.write_ply(path, post[0].cpu().numpy(), m.template.faces, colours)
+        return path
+
     # ------------------------------------------------------------ the whole run
     def _generator(self, step):
         return torch.Generator().manual_seed(self.seed + step)
@@ -578,12 +926,20 @@ class Tester:
         _dump(self._path("eval_metrics.json"), out)
         return out
 
-    STEPS = ("traversals", "embeddings", "classifiers", "generation", "metrics", "interpolate", "tsne")
+    STEPS = ("traversals", "embeddings", "classifiers", "generation", "metrics", "interpolate", "tsne", "plan",
+             "prepost")
+    # what the steps ``plan`` and ``prepost`` work on (``evaluate.py --patient / --pairs / --pairs-root``)
+    plan_patients = ()
+    pairs_table = pairs_root = None
 
     def run(self, step):
-        """One step of the evaluation by name (``STEPS``); ``interpolate`` and
-        ``tsne`` are not part of :meth:`__call__`, as in the reference (whose
-        ``__call__`` draws the LDA embedding only)."""
+        """One step of the evaluation by name (``STEPS``); ``interpolate``,
+        ``tsne``, ``plan`` and ``prepost`` are not part of :meth:`__call__`, as
+        in the reference (whose ``__call__`` draws the LDA embedding only).
+        ``plan`` runs :meth:`classify_and_project` and
+        :meth:`interpolate_syndrome_to_normal` on every mesh of
+        ``plan_patients``, ``prepost`` :meth:`evaluate_all_pre_post_pairs` on
+        ``pairs_table`` under ``pairs_root``."""
         if step == "traversals":
             return self.latent_traversals(use_z_stats=False, animations=self.animations)
         if step == "embeddings":
@@ -599,6 +955,16 @@ class Tester:
             return self.interpolate(animations=self.animations)
         if step == "tsne":
             return self.tsne_embeddings(generator=self._generator(5))
+        if step == "plan":
+            if not self.plan_patients:
+                raise ValueError("the step 'plan' needs plan_patients (evaluate.py --patient PATH)")
+            return [(self.classify_and_project(p), self.interpolate_syndrome_to_normal(p, animations=self.animations))
+                    for p in self.plan_patients]
+        if step == "prepost":
+            if self.pairs_table is None or self.pairs_root is None:
+                raise ValueError("the step 'prepost' needs pairs_table and pairs_root "
+                                 "(evaluate.py --pairs FILE --pairs-root DIR)")
+            return self.evaluate_all_pre_post_pairs(self.pairs_root, self.pairs_table)
         raise ValueError(f"unknown step {step!r}; expected one of {self.STEPS}")
 
     def __call__(self):
@@ -634,7 +1000,17 @@ def evaluate_main(argv=None):
                         help="latent pairs of the diversity figure")
     parser.add_argument("--only", default=None, metavar="NAME[,NAME]",
                         help="run only these steps: " + ", ".join(Tester.STEPS))
+    parser.add_argument("--patient", action="append", default=[], metavar="PATH",
+                        help="a patient's mesh file for the step 'plan' (may be given several times)")
+    parser.add_argument("--pairs", default=None, metavar="FILE",
+                        help="the table (.csv or .xlsx) of pre- / post-operative pairs for the step 'prepost'")
+    parser.add_argument("--pairs-root", default=None, metavar="DIR", help="the folder of the meshes --pairs names")
     opts = parser.parse_args(argv)
+    asked = [s for s in (opts.only or "").split(",") if s]
+    if "plan" in asked and not opts.patient:
+        parser.error("--only plan needs at least one --patient PATH")
+    if "prepost" in asked and (opts.pairs is None or opts.pairs_root is None):
+        parser.error("--only prepost needs --pairs FILE and --pairs-root DIR")
 
     from . import data as D
     from . import manager as M
@@ -661,6 +1037,7 @@ def evaluate_main(argv=None):
     tester = Tester(manager, norm if config["data"].get("normalize_data", True) else None, train_set, test_set,
                     output_directory, config, seed=opts.seed, animations=not opts.no_animations,
                     diversity_samples=opts.diversity_samples)
+    tester.plan_patients, tester.pairs_table, tester.pairs_root = tuple(opts.patient), opts.pairs, opts.pairs_root
     if only is None:
         tester()
     else:

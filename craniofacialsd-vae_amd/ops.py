@@ -2210,3 +2210,135 @@ def tsne_step(y, update, gains, csr, momentum, learning_rate, exaggeration=1.0, 
          ptr(workspace), nbytes, n, splits, float(exaggeration), float(momentum), float(learning_rate), want,
          stream_ptr())
     return (grad, result) if want_error else grad
+
+
+# ------------------------------------------------------------------ surgical planning
+PLAN_MAX_LEVELS, PLAN_MAX_STEPS = _H["CFSD_PLAN_MAX_LEVELS"], _H["CFSD_PLAN_MAX_STEPS"]
+PLAN_MAX_FIRST, PLAN_MAX_WINDOWS = _H["CFSD_PLAN_MAX_FIRST"], _H["CFSD_PLAN_MAX_WINDOWS"]
+
+
+def _host_array(ctype, values):
+    """A HOST argument of an entry point: a ctypes array and its address."""
+    arr = (ctype * len(values))(*values)
+    return arr, ctypes.cast(arr, ctypes.c_void_p)
+
+
+def _plan_levels(levels):
+    levels = [float(v) for v in levels]
+    if not 1 <= len(levels) <= PLAN_MAX_LEVELS:
+        raise ValueError(f"{len(levels)} levels: 1..{PLAN_MAX_LEVELS} are supported")
+    if any(not 0.0 < v < float("inf") for v in levels) or any(b >= a for a, b in zip(levels, levels[1:])):
+        raise ValueError(f"levels {levels}: expected positive, finite, strictly descending numbers")
+    return levels
+
+
+def plan_targets(z, mean, whiten, levels=(3.0, 2.0, 1.0), steps=5000, cols=None):
+    """The crossings of ``Tester.interpolate_syndrome_to_normal``
+    (``test.py:663-704``) for every row of ``z`` ``[n, ld]`` at once
+    (``cfsd_plan_targets``): ``mean`` ``[d]`` and ``whiten`` ``[d, d]`` are the
+    healthy class of a QDA over the column window ``cols = (col0, d)``
+    (default: every column), ``levels`` descending Mahalanobis radii, ``steps``
+    the points of the ``torch.linspace`` from the row to ``mean``.  Returns
+    ``(maha [n], index [n, S] int32, targets [n, S + 1, d])``: the row's
+    distance, per level the first grid point within it (0 for a row already
+    inside) and that point; ``targets[:, S]`` is ``mean``."""
+    n, ld, col0, d = _window(z, cols)
+    _need(mean, (d,), name="mean")
+    _need(whiten, (d, d), name="whiten")
+    if mean.device != z.device or whiten.device != z.device:
+        raise ValueError(f"mean / whiten are on {mean.device} / {whiten.device}, z on {z.device}")
+    levels, steps = _plan_levels(levels), int(steps)
+    if not 2 <= steps <= PLAN_MAX_STEPS:
+        raise ValueError(f"steps={steps} outside 2..{PLAN_MAX_STEPS}")
+    s = len(levels)
+    if n * ld >= 2 ** 31 or n * (s + 1) * d >= 2 ** 31:
+        raise ValueError("plan_targets: n x ld or n x (levels + 1) x d >= 2^31")
+    maha = torch.empty((n,), dtype=torch.float32, device=z.device)
+    index = torch.empty((n, s), dtype=torch.int32, device=z.device)
+    targets = torch.empty((n, s + 1, d), dtype=torch.float32, device=z.device)
+    keep, lv = _host_array(ctypes.c_float, levels)
+    call("cfsd_plan_targets", ptr(z), ptr(mean), ptr(whiten), lv, ptr(maha), ptr(index), ptr(targets), n, ld, col0, d,
+         s, steps, stream_ptr())
+    return maha, index, targets
+
+
+def plan_tables(z, targets, mask=None, n_first=8):
+    """The latent tables of ``test.py:706-740`` (``cfsd_plan_tables``): ``z``
+    ``[n, L]``, ``targets`` ``[n, S + 1, L]`` of a full-width
+    :func:`plan_targets`, ``mask`` ``[P, L]`` uint8 the columns each procedure
+    moves (``None``: no procedure).  Returns ``(tables [n, 1 + P, n_first + S,
+    L], dist [n, 1 + P, S + 1])``: group 0 moves every column (``n_first``
+    rows from ``z`` to the first target, then the other targets), group ``1 +
+    p`` only procedure ``p``'s columns; ``dist`` the mean squared distance of
+    the last ``S + 1`` rows to ``targets[:, S]`` (``d3, d2, d1, dm``)."""
+    _need(z, None, name="z")
+    if z.dim() != 2 or z.shape[0] < 1 or not 1 <= z.shape[1] <= CLS_MAX_D:
+        raise ValueError(f"z: shape {tuple(z.shape)}, expected [n >= 1, 1..{CLS_MAX_D}]")
+    n, lat = int(z.shape[0]), int(z.shape[1])
+    _need(targets, None, name="targets")
+    if targets.dim() != 3 or targets.shape[0] != n or targets.shape[2] != lat or \
+            not 2 <= targets.shape[1] <= PLAN_MAX_LEVELS + 1:
+        raise ValueError(f"targets: shape {tuple(targets.shape)}, expected [{n}, 2..{PLAN_MAX_LEVELS + 1}, {lat}]")
+    s = int(targets.shape[1]) - 1
+    p = 0
+    if mask is not None:
+        _need(mask, None, torch.uint8, "mask")
+        if mask.dim() != 2 or mask.shape[1] != lat:
+            raise ValueError(f"mask: shape {tuple(mask.shape)}, expected [P, {lat}]")
+        p = int(mask.shape[0])
+    for name, t in (("targets", targets), ("mask", mask)):
+        if t is not None and t.device != z.device:
+            raise ValueError(f"{name} is on {t.device}, z on {z.device}")
+    n_first = int(n_first)
+    if not 1 <= n_first <= PLAN_MAX_FIRST:
+        raise ValueError(f"n_first={n_first} outside 1..{PLAN_MAX_FIRST}")
+    f = n_first + s
+    if n * (1 + p) * f * lat >= 2 ** 31:
+        raise ValueError("plan_tables: n x (1 + P) x frames x latent >= 2^31")
+    tables = torch.empty((n, 1 + p, f, lat), dtype=torch.float32, device=z.device)
+    dist = torch.empty((n, 1 + p, s + 1), dtype=torch.float32, device=z.device)
+    call("cfsd_plan_tables", ptr(z), ptr(targets), ptr(mask) if p else None, ptr(tables), ptr(dist), n, lat, s, p,
+         n_first, stream_ptr())
+    return tables, dist
+
+
+PAIR_RAW = ("maha_pre", "maha_post", "l2_pre", "l2_post", "cosine", "maha_displacement")  # raw[..., q]
+
+
+def pair_metrics(z_pre, z_post, windows, mean, whiten):
+    """The raw quantities of ``Tester.evaluate_pre_post_pair``
+    (``test.py:992-1081``) for ``N`` pairs and ``W`` column windows in one
+    launch (``cfsd_pair_metrics``): ``z_pre`` / ``z_post`` ``[N, L]``;
+    ``windows`` a host sequence of ``(col0, d, mean offset, whiten offset)``
+    into the packed device arrays ``mean`` / ``whiten`` (flat: per window the
+    healthy mean ``[d]`` and whitening matrix ``[d, d]``).  Returns ``raw``
+    ``[N, W, 6]`` in the order of ``PAIR_RAW``; the cosine of a zero
+    displacement is NaN."""
+    _need(z_pre, None, name="z_pre")
+    if z_pre.dim() != 2 or z_pre.shape[0] < 1 or z_pre.shape[1] < 1:
+        raise ValueError(f"z_pre: shape {tuple(z_pre.shape)}, expected [N >= 1, L >= 1]")
+    n, lat = int(z_pre.shape[0]), int(z_pre.shape[1])
+    _need(z_post, (n, lat), name="z_post")
+    _need(mean, None, name="mean")
+    _need(whiten, None, name="whiten")
+    if mean.dim() != 1 or whiten.dim() != 1 or not mean.numel() or not whiten.numel():
+        raise ValueError(f"mean {tuple(mean.shape)} / whiten {tuple(whiten.shape)}: expected two flat packed arrays")
+    for name, t in (("z_post", z_post), ("mean", mean), ("whiten", whiten)):
+        if t.device != z_pre.device:
+            raise ValueError(f"{name} is on {t.device}, z_pre on {z_pre.device}")
+    rows = [tuple(int(v) for v in w) for w in windows]
+    if not 1 <= len(rows) <= PLAN_MAX_WINDOWS or any(len(w) != 4 for w in rows):
+        raise ValueError(f"{len(rows)} windows: 1..{PLAN_MAX_WINDOWS} rows of (col0, d, mean offset, whiten offset)")
+    for i, (col0, d, mo, wo) in enumerate(rows):
+        if col0 < 0 or d < 1 or col0 + d > lat or d > CLS_MAX_D:
+            raise ValueError(f"window {i}: columns [{col0}, {col0 + d}) outside [0, {lat}) or wider than {CLS_MAX_D}")
+        if mo < 0 or mo + d > mean.numel() or wo < 0 or wo + d * d > whiten.numel():
+            raise ValueError(f"window {i}: offsets {mo} / {wo} past the packed mean ({mean.numel()}) or whiten "
+                             f"({whiten.numel()})")
+    if n * lat >= 2 ** 31 or n * len(rows) * 6 >= 2 ** 31 or max(mean.numel(), whiten.numel()) >= 2 ** 31:
+        raise ValueError("pair_metrics: n x L, n x W x 6 or a packed array >= 2^31")
+    raw = torch.empty((n, len(rows), 6), dtype=torch.float32, device=z_pre.device)
+    keep, win = _host_array(ctypes.c_int32, [v for w in rows for v in w])
+    call("cfsd_pair_metrics", ptr(z_pre), ptr(z_post), win, ptr(mean), ptr(whiten), ptr(raw), n, lat, len(rows),
+         int(mean.numel()), int(whiten.numel()), stream_ptr())
+    return raw

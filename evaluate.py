@@ -1,5 +1,6 @@
 """``python evaluate.py --id ID [--output_path P] [--precision fp32|bf16] [--seed S]
-[--no-animations] [--diversity-samples N] [--only NAME[,NAME]]``: evaluate the
+[--no-animations] [--diversity-samples N] [--only NAME[,NAME]] [--patient PATH]...
+[--pairs FILE --pairs-root DIR]``: evaluate the
 model trained as ``ID`` (the reference's ``python test.py --id ID``,
 test.py:57-79, 1443-1480) on the MI355X path
 (craniofacialsd-vae_amd/evaluation.py): latent traversals with their
@@ -9,7 +10,12 @@ classifiers, their test reports.  Everything is written into
 ``<output_path>/outputs/<ID>``.  ``--only`` runs single steps: traversals,
 embeddings, classifiers, generation, metrics, interpolate, tsne (the t-SNE
 embedding of the train and test latents, ``tsne_embeddings.npz``; it needs no
-classifiers and is not part of the whole run, as in the reference)."""
+classifiers and is not part of the whole run, as in the reference), plan
+(``--patient PATH``, once per patient: the patient classified, projected and
+moved to the healthy distribution, procedure by procedure, under
+``interpolations/``) and prepost (``--pairs FILE --pairs-root DIR``: the
+surgical-effectiveness metrics of every pre- / post-operative pair of the
+table, under ``pre_post_eval/``); neither is part of the whole run either."""
 import os
 import sys
 

@@ -1098,6 +1098,77 @@ int cfsd_tsne_update(float* y, float* update, float* gains, float* grad, float* 
                      size_t workspace_bytes, int n, int splits, float exaggeration, float momentum,
                      float learning_rate, int want_error, void* stream);
 
+/* ---------------------------------------------------------------- surgical planning
+ * The arithmetic of Tester.interpolate_syndrome_to_normal (test.py:652-748)
+ * and Tester.evaluate_pre_post_pair (test.py:972-1088), ABI 4.22.  One
+ * CFSD_CLS_MAX_D-thread workgroup per row of work.  Operands are fp32, every
+ * product and sum is float64: thread k forms component k of a whitened vector
+ * (ascending j), squared norms and dot products meet in one halving tree over
+ * CFSD_CLS_MAX_D slots (part[t] += part[t + w], w = 64, ..., 1; slots past the
+ * width hold 0).  No atomics; a row's result depends on no other row of the
+ * call and two calls give the same bits.  Every entry point checks its
+ * arguments before any HIP call.
+ *
+ * The grid: point i of torch.linspace(s, e, steps) in fp32, nothing fused,
+ *   step = (e - s) / (steps - 1),
+ *   g(i) = s + step * i            for i < steps / 2,
+ *          e - step * (steps-1-i)  otherwise            (so g(steps - 1) = e).
+ *
+ * cfsd_plan_targets: z [n, ld], of which the window [col0, col0 + d) is read,
+ * d <= CFSD_CLS_MAX_D; mean [d] and whiten [d, d] of the healthy class of a
+ * QDA; levels a HOST array of n_levels <= CFSD_PLAN_MAX_LEVELS positive, finite,
+ * strictly descending floats (the reference: 3, 2, 1); 2 <= steps <=
+ * CFSD_PLAN_MAX_STEPS (the reference: 5000).  Per row p, with s = z[p, col0 + j]
+ * and e = mean[j] per column:
+ *   maha[p] = |(z_p - mean) whiten|, rounded to fp32;
+ *   index[p, k] (int32): along the segment the distance shrinks linearly, so
+ *     i0 = ceil((steps - 1)(1 - levels[k] / maha)) clamped to [0, steps - 1]
+ *     (float64, the unrounded maha); then the grid points i0 - 1, i0, i0 + 1
+ *     that exist are evaluated, |(g(i) - mean) whiten|^2 <= levels[k]^2, and the
+ *     lowest one inside wins (i0 + 1, clamped, if none is).  0 for a row that is
+ *     already inside, and for a row equal to the mean;
+ *   targets[p, k, :] = g(index[p, k]) for k < n_levels, targets[p, n_levels, :]
+ *     = mean bit for bit: [n, n_levels + 1, d].
+ *
+ * cfsd_plan_tables: z [n, L] and targets [n, S + 1, L] of a full-width
+ * cfsd_plan_targets call (L <= CFSD_CLS_MAX_D, S = n_levels); mask [P, L]
+ * uint8, the columns procedure p moves (P = n_procedures >= 0; NULL allowed for
+ * P = 0); 1 <= n_first <= CFSD_PLAN_MAX_FIRST (the reference: 8).  With F =
+ * n_first + S:
+ *   tables [n, 1 + P, F, L].  Group 0 moves every column: rows r < n_first are
+ *     the grid from z to targets[:, 0] in n_first steps (n_first = 1: z), rows
+ *     n_first - 1 + t are targets[:, t], t = 1..S.  Group 1 + p holds the same
+ *     in the columns with mask[p] != 0 and z, bit for bit, in every other.
+ *   dist [n, 1 + P, S + 1]: dist[., g, t] = mean over all L columns of
+ *     (tables[., g, n_first - 1 + t, j] - targets[., S, j])^2, the reference's
+ *     d3, d2, d1, dm (compute_mse_loss against the healthy mean), rounded once.
+ *
+ * cfsd_pair_metrics: z_pre, z_post [n, L]; windows a HOST array [W, 4] int32 of
+ * (col0, d, offset into mean, offset into whiten), W <= CFSD_PLAN_MAX_WINDOWS,
+ * d <= CFSD_CLS_MAX_D; mean (mean_floats floats) and whiten (whiten_floats
+ * floats) the packed healthy means [d] and whitening matrices [d, d] of the
+ * windows.  raw [n, W, 6], per pair and window with a = pre - mean, b = post -
+ * mean, v = post - pre over the window's columns:
+ *   0: |a whiten|   1: |b whiten|   2: |a|   3: |b|
+ *   4: (v . -a) / (|v| |a|), the cosine between the displacement and the ideal
+ *      trajectory; NaN (0 / 0) when either is the zero vector, as numpy gives
+ *      the reference; no other entry becomes NaN because of it
+ *   5: |v whiten|
+ * CFSD_EINVAL: a null pointer, sizes < 1, a window outside [0, L) or wider
+ * than CFSD_CLS_MAX_D, an offset past mean_floats / whiten_floats. */
+#define CFSD_PLAN_MAX_LEVELS 8
+#define CFSD_PLAN_MAX_STEPS 1048576
+#define CFSD_PLAN_MAX_FIRST 64
+#define CFSD_PLAN_MAX_WINDOWS 64
+int cfsd_plan_targets(const float* z, const float* mean, const float* whiten, const float* levels, float* maha,
+                      int32_t* index, float* targets, int n, int ld, int col0, int d, int n_levels, int steps,
+                      void* stream);
+int cfsd_plan_tables(const float* z, const float* targets, const uint8_t* mask, float* tables, float* dist, int n,
+                     int latent, int n_levels, int n_procedures, int n_first, void* stream);
+int cfsd_pair_metrics(const float* z_pre, const float* z_post, const int32_t* windows, const float* mean,
+                      const float* whiten, float* raw, int n, int latent, int n_windows, int mean_floats,
+                      int whiten_floats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
