@@ -27,7 +27,12 @@ distribution in closed form (``ops.plan_targets``), the latent tables of the
 planned procedures (``ops.plan_tables``) and the raw quantities of every pair
 and region in one launch (``ops.pair_metrics``).  The figures the reference
 draws its points into become JSON files of those points.  Out of scope: the
-``LinearSVC`` and every plot.
+``LinearSVC`` and the plots other than the embedding figures.
+
+The embedding figures (class-density maps, paths to normal and pre / post
+arrows on them) are drawn on the device by ``figures.py`` over three kernels
+of ``csrc/figures.hip``: ``embedding_figures``, ``plan_figures``,
+``prepost_figures``, the step ``figures``.
 
 Latents are decoded in chunks of exactly ``batch_size ** 2`` rows (the last
 one padded), so a decoded head does not depend on how many others were asked
@@ -40,7 +45,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops, precompute, rendering, tsne
+from . import figures, ops, precompute, rendering, tsne
 
 N_STEPS = 10  # frames per latent variable of a traversal (test.py:144)
 
@@ -912,6 +917,130 @@ class Tester:
         precompute.write_ply(path, post[0].cpu().numpy(), m.template.faces, colours)
         return path
 
+    # ------------------------------------------------------------ the embedding figures
+    def embedding_figures(self, mode="lda"):
+        """``plot_embeddings`` and ``plot_embeddings_per_region``
+        (``test.py:1161-1321``) drawn by :func:`figures.embedding_figures`.
+        ``lda``: the arrays :meth:`embeddings` writes (needs classifiers), files
+        ``lda_emb_*.png``, ``emb_all_train.png`` and ``emb_all_train_dist.png``;
+        ``tsne``: the points of ``tsne_embeddings.npz`` (fitted by
+        :meth:`tsne_embeddings` when the file is not there), prefix ``tsne``, no
+        region figure, no classifiers.  Returns the base images and layouts,
+        which are kept in ``figure_bases[mode]`` for :meth:`plan_figures` and
+        :meth:`prepost_figures`."""
+        if mode == "lda":
+            data = np.load(self.embeddings())
+            regions = {str(k): data[f"region_{i}"] for i, k in enumerate(data["region_keys"])}
+        elif mode == "tsne":
+            path = self._path("tsne_embeddings.npz")
+            data = np.load(path if os.path.exists(path) else self.tsne_embeddings(generator=self._generator(5)))
+            regions = None
+        else:
+            raise NotImplementedError(f"embedding mode {mode!r}")
+        xy = np.stack([data["x1"], data["x2"]], axis=1)
+        out = figures.embedding_figures(xy, data["class"], data["is_test"], data["augmented"], self._out_dir,
+                                        prefix=mode, regions=regions, device=self._device)
+        self.figure_bases = {**self.figure_bases, mode: out}
+        return out
+
+    def _lda_bases(self):
+        bases = self.figure_bases.get("lda") or self.embedding_figures("lda")
+        return bases["distributions"], bases.get("all_train_dist")
+
+    def _lda_points(self, z):
+        xy = self._manager.lda_project_latents_in_2d(z)
+        return torch.stack([xy[:, 0], xy[:, -1]], dim=1).cpu().tolist()
+
+    def plan_figures(self, patient_path, animations=None):
+        """``_render_embed_save_z_interpolations`` (``test.py:750-833``): the
+        path of :meth:`plan_to_normal` scattered on the density maps.  Per group,
+        under ``interpolations/<id>_<name>/``: ``<id>_<name>_emb_interpolate.png``
+        (every point of the path on ``lda_emb_distributions.png``),
+        ``<id>_<name>_emb_r_interpolate.png`` (each region LDA's points on
+        ``emb_all_train_dist.png``; with region classifiers) and, with
+        animations, the two ``.apng`` at 4 fps, one point per frame.  Returns
+        ``{group: {file kind: path}}``."""
+        self._need_classifiers()
+        animations = self.animations if animations is None else animations
+        main, regional = self._lda_bases()
+        pid = self._mesh_id(patient_path)
+        plan = self.plan_to_normal(self._load_and_encode(patient_path))
+        n_groups, n_frames, latent = plan["tables"].shape[1:]
+        z_all = plan["tables"].view(n_groups * n_frames, latent)
+        lda_xy, region_xy = self._lda_points(z_all), self._region_projections(z_all)
+        files = {}
+        for g, name in enumerate(plan["groups"]):
+            rows = range(g * n_frames, (g + 1) * n_frames)
+            save_id = f"{pid}_{name}"
+            out = os.path.join(self._path("interpolations"), save_id)
+            os.makedirs(out, exist_ok=True)
+            sheets = [("emb", main, [[{"panel": 0, "kind": "disc", "xy": lda_xy[r], "colour": figures.PATH_COLOUR}]
+                                     for r in rows])]
+            if regional is not None and region_xy:
+                sheets.append(("emb_r", regional, [[{"panel": k, "kind": "disc", "xy": v[r],
+                                                     "colour": figures.PATH_COLOUR} for k, v in region_xy.items()]
+                                                   for r in rows]))
+            files[name] = {}
+            for tag, base, frames in sheets:
+                whole = figures.overlay(base["image"], base["layout"], [[m for f in frames for m in f]])
+                files[name][tag] = rendering.save_png(os.path.join(out, f"{save_id}_{tag}_interpolate.png"), whole[0])
+                if animations:
+                    files[name][tag + "_animation"] = rendering.save_apng(
+                        os.path.join(out, f"{save_id}_{tag}_interpolate.apng"),
+                        figures.overlay(base["image"], base["layout"], frames), fps=4)
+        return files
+
+    def prepost_figures(self, z_pre, z_post, patient_ids):
+        """``_project_pre_post_pair`` (``test.py:1090-1136``): per patient
+        ``pre_post_eval_plots/<pid>_emb.png`` (on ``lda_emb_distributions.png``)
+        and, with region classifiers, ``<pid>_emb_r.png`` (on
+        ``emb_all_train_dist.png``): the pre-operative point, the
+        post-operative point and an arrow from the first to the second.
+        Returns ``{pid: {file kind: path}}``."""
+        self._need_classifiers()
+        main, regional = self._lda_bases()
+        z_pre = z_pre.detach().to(self._device, torch.float32).contiguous()
+        z_post = z_post.detach().to(self._device, torch.float32).contiguous()
+        if z_pre.shape != z_post.shape or len(patient_ids) != len(z_pre):
+            raise ValueError(f"z_pre {tuple(z_pre.shape)}, z_post {tuple(z_post.shape)} and {len(patient_ids)} ids "
+                             "must name the same pairs")
+        out = self._path("pre_post_eval_plots")
+        os.makedirs(out, exist_ok=True)
+
+        def pair(panel, a, b):
+            return [{"panel": panel, "kind": "arrow", "xy": a, "xy2": b, "colour": figures.POST_COLOUR},
+                    {"panel": panel, "kind": "disc", "xy": a, "colour": figures.PRE_COLOUR},
+                    {"panel": panel, "kind": "disc", "xy": b, "colour": figures.POST_COLOUR}]
+
+        sheets = [("emb", main, [pair(0, a, b) for a, b in zip(self._lda_points(z_pre), self._lda_points(z_post))])]
+        r_pre, r_post = self._region_projections(z_pre), self._region_projections(z_post)
+        if regional is not None and r_pre:
+            sheets.append(("emb_r", regional, [[m for k in r_pre for m in pair(k, r_pre[k][i], r_post[k][i])]
+                                               for i in range(len(patient_ids))]))
+        files = {str(pid): {} for pid in patient_ids}
+        for tag, base, frames in sheets:
+            images = figures.overlay(base["image"], base["layout"], frames)
+            for i, pid in enumerate(patient_ids):
+                files[str(pid)][tag] = rendering.save_png(os.path.join(out, f"{pid}_{tag}.png"), images[i])
+        return files
+
+    def all_figures(self):
+        """The step ``figures``: the LDA embedding figures with classifiers
+        (the t-SNE ones without), the plan figures of every mesh of
+        ``plan_patients`` and, with ``pairs_table`` and ``pairs_root``, the pair
+        figures of every row of the table."""
+        if not self.has_classifiers:
+            return {"tsne": self.embedding_figures("tsne")}
+        out = {"lda": self.embedding_figures("lda"),
+               "plan": [self.plan_figures(p) for p in self.plan_patients]}
+        if self.pairs_table is not None and self.pairs_root is not None:
+            frame = read_pairs_table(self.pairs_table)
+            z_pre = torch.cat([self._load_and_encode(os.path.join(str(self.pairs_root), n)) for n in frame["Pre name"]])
+            z_post = torch.cat([self._load_and_encode(os.path.join(str(self.pairs_root), n))
+                                for n in frame["Post name"]])
+            out["prepost"] = self.prepost_figures(z_pre, z_post, list(frame["PID"]))
+        return out
+
     # ------------------------------------------------------------ the whole run
     def _generator(self, step):
         return torch.Generator().manual_seed(self.seed + step)
@@ -927,14 +1056,17 @@ class Tester:
         return out
 
     STEPS = ("traversals", "embeddings", "classifiers", "generation", "metrics", "interpolate", "tsne", "plan",
-             "prepost")
+             "prepost", "figures")
     # what the steps ``plan`` and ``prepost`` work on (``evaluate.py --patient / --pairs / --pairs-root``)
     plan_patients = ()
     pairs_table = pairs_root = None
+    # mode -> what figures.embedding_figures returned: the base images the plan and pair figures are drawn on
+    figure_bases = {}
 
     def run(self, step):
         """One step of the evaluation by name (``STEPS``); ``interpolate``,
-        ``tsne``, ``plan`` and ``prepost`` are not part of :meth:`__call__`, as
+        ``tsne``, ``plan``, ``prepost`` and ``figures`` (:meth:`all_figures`)
+        are not part of :meth:`__call__`, as
         in the reference (whose ``__call__`` draws the LDA embedding only).
         ``plan`` runs :meth:`classify_and_project` and
         :meth:`interpolate_syndrome_to_normal` on every mesh of
@@ -965,6 +1097,8 @@ class Tester:
                 raise ValueError("the step 'prepost' needs pairs_table and pairs_root "
                                  "(evaluate.py --pairs FILE --pairs-root DIR)")
             return self.evaluate_all_pre_post_pairs(self.pairs_root, self.pairs_table)
+        if step == "figures":
+            return self.all_figures()
         raise ValueError(f"unknown step {step!r}; expected one of {self.STEPS}")
 
     def __call__(self):

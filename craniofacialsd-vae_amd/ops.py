@@ -2342,3 +2342,127 @@ def pair_metrics(z_pre, z_post, windows, mean, whiten):
     call("cfsd_pair_metrics", ptr(z_pre), ptr(z_post), win, ptr(mean), ptr(whiten), ptr(raw), n, lat, len(rows),
          int(mean.numel()), int(whiten.numel()), stream_ptr())
     return raw
+
+
+# ------------------------------------------------------------------ embedding figures
+KDE_CHUNK, KDE_MAX_G = _H["CFSD_KDE_CHUNK"], _H["CFSD_KDE_MAX_G"]  # points per LDS chunk of cfsd_kde2d; largest grid side
+PRIM_ROUND, PRIM_FLOATS, PRIM_MAX = _H["CFSD_PRIM_ROUND"], _H["CFSD_PRIM_FLOATS"], _H["CFSD_PRIM_MAX"]
+PRIM_DISC, PRIM_SEGMENT, PRIM_TRIANGLE = _H["CFSD_PRIM_DISC"], _H["CFSD_PRIM_SEGMENT"], _H["CFSD_PRIM_TRIANGLE"]
+FIG_MAX_SIZE = _H["CFSD_FIG_MAX_SIZE"]
+SHADE_MAX_PANELS, SHADE_MAX_LAYERS = _H["CFSD_SHADE_MAX_PANELS"], _H["CFSD_SHADE_MAX_LAYERS"]
+SHADE_MAX_LEVELS = _H["CFSD_SHADE_MAX_LEVELS"]
+SHADE_PANEL_DOUBLES, SHADE_LAYER_DOUBLES = _H["CFSD_SHADE_PANEL_DOUBLES"], _H["CFSD_SHADE_LAYER_DOUBLES"]
+
+
+def _host_table(values, dtype, cols, name):
+    """A HOST table of an entry point: a C-contiguous NumPy array ``[rows,
+    cols]`` (``cols`` None: flat) and its address; keep the array alive over
+    the call."""
+    import numpy as np
+    arr = np.ascontiguousarray(np.asarray(values, dtype=dtype))
+    if (cols is None and arr.ndim != 1) or (cols is not None and (arr.ndim != 2 or arr.shape[1] != cols)):
+        raise ValueError(f"{name}: shape {arr.shape}, expected " + ("[n]" if cols is None else f"[n, {cols}]"))
+    return arr, ctypes.c_void_p(arr.ctypes.data)
+
+
+def kde2d(points, set_ptr, params, grid_size):
+    """``S`` Gaussian kernel density estimates on ``grid_size`` x ``grid_size``
+    grids in one call (``cfsd_kde2d``), float64 throughout: ``points`` ``[N,
+    2]`` float64 (device) grouped by set through the host sequence ``set_ptr``
+    ``[S + 1]``; ``params`` a host table ``[S, 8]`` per set of ``L00, L10, L11``
+    (the lower-triangular factor of the inverse kernel covariance), ``scale``,
+    ``lo0, step0, lo1, step1``.  Returns ``density`` ``[S, G, G]``:
+    ``density[s, i, j] = scale * sum_k exp(-|L^T (g_ij - x_k)|^2 / 2)``, the sum
+    in point order; zeros for an empty set."""
+    import numpy as np
+    _need(points, None, torch.float64, "points")
+    if points.dim() != 2 or points.shape[1] != 2:
+        raise ValueError(f"points: shape {tuple(points.shape)}, expected [N, 2]")
+    n, g = int(points.shape[0]), int(grid_size)
+    sp, sp_p = _host_table(set_ptr, np.int32, None, "set_ptr")
+    if sp.size < 2:
+        raise ValueError("set_ptr: at least one set is required")
+    s = sp.size - 1
+    if sp[0] < 0 or sp[-1] > n or np.any(np.diff(sp) < 0):
+        raise ValueError(f"set_ptr must ascend within [0, {n}]")
+    par, par_p = _host_table(params, np.float64, 8, "params")
+    if par.shape[0] != s:
+        raise ValueError(f"params: {par.shape[0]} rows for {s} sets")
+    if not np.all(np.isfinite(par)) or np.any(par[:, 5] <= 0) or np.any(par[:, 7] <= 0):
+        raise ValueError("params must be finite, with positive grid steps")
+    if not 2 <= g <= KDE_MAX_G:
+        raise ValueError(f"grid_size={g} outside 2..{KDE_MAX_G}")
+    if n >= 2 ** 30 or s * g * g >= 2 ** 31:
+        raise ValueError("kde2d: N >= 2^30 or S x G x G >= 2^31")
+    density = torch.empty((s, g, g), dtype=torch.float64, device=points.device)
+    call("cfsd_kde2d", ptr(points) if n else None, sp_p, par_p, ptr(density), n, s, g, stream_ptr())
+    return density
+
+
+def density_shade(image, grids, panels, layers):
+    """Shade density layers into ``image`` ``[3, H, W]`` fp32 in place
+    (``cfsd_density_shade``): ``grids`` a flat float64 device tensor holding the
+    density grids; ``panels`` a host table ``[P, 8]`` of ``px0, py0, pw, ph,
+    xlo, xhi, ylo, yhi``; ``layers`` a host table ``[n, 24]`` of ``panel, grid
+    offset, G0, G1, lo0, step0, lo1, step1, K, 8 levels, r, g, b, a, fill, line,
+    0`` (``include/cfsd.h`` states the arithmetic).  Layers apply in order;
+    pixels outside every panel are not written.  Returns ``image``."""
+    import numpy as np
+    _need(image, None, name="image")
+    if image.dim() != 3 or image.shape[0] != 3:
+        raise ValueError(f"image: shape {tuple(image.shape)}, expected [3, H, W]")
+    h, w = int(image.shape[1]), int(image.shape[2])
+    if not (1 <= h <= FIG_MAX_SIZE and 1 <= w <= FIG_MAX_SIZE):
+        raise ValueError(f"image {h} x {w}: sides of 1..{FIG_MAX_SIZE} are supported")
+    _need(grids, None, torch.float64, "grids")
+    if grids.dim() != 1 or grids.numel() < 4 or grids.numel() >= 2 ** 31 or grids.device != image.device:
+        raise ValueError(f"grids: expected a flat float64 tensor of 4..2^31 values on {image.device}")
+    pan, pan_p = _host_table(panels, np.float64, SHADE_PANEL_DOUBLES, "panels")
+    lay, lay_p = _host_table(layers, np.float64, SHADE_LAYER_DOUBLES, "layers")
+    if not 1 <= pan.shape[0] <= SHADE_MAX_PANELS:
+        raise ValueError(f"{pan.shape[0]} panels: 1..{SHADE_MAX_PANELS} are supported")
+    if not 1 <= lay.shape[0] <= SHADE_MAX_LAYERS:
+        raise ValueError(f"{lay.shape[0]} layers: 1..{SHADE_MAX_LAYERS} are supported")
+    k = lay[:, 8]
+    if np.any(k != np.floor(k)) or np.any(k < 1) or np.any(k > SHADE_MAX_LEVELS):
+        raise ValueError(f"layers: K outside 1..{SHADE_MAX_LEVELS}")
+    call("cfsd_density_shade", ptr(image), ptr(grids), pan_p, lay_p, h, w, pan.shape[0], lay.shape[0],
+         int(grids.numel()), stream_ptr())
+    return image
+
+
+def draw_primitives(images, prims, prim_ptr):
+    """Composite discs, segments and triangles into ``images`` ``[B, 3, H, W]``
+    fp32 in place (``cfsd_draw_primitives``): ``prims`` a host table ``[n, 16]``
+    of ``kind, x0, y0, x1, y1, x2, y2, r, red, green, blue, alpha, clip x0, y0,
+    x1, y1`` (``PRIM_DISC`` / ``PRIM_SEGMENT`` / ``PRIM_TRIANGLE``, pixels),
+    ``prim_ptr`` the host sequence ``[B + 1]``: image ``b`` takes the rows
+    ``prim_ptr[b] .. prim_ptr[b + 1]`` in order.  The tables are copied to the
+    device here.  Returns ``images``."""
+    import numpy as np
+    _need(images, None, name="images")
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError(f"images: shape {tuple(images.shape)}, expected [B, 3, H, W]")
+    b, _, h, w = (int(v) for v in images.shape)
+    if not (1 <= h <= FIG_MAX_SIZE and 1 <= w <= FIG_MAX_SIZE):
+        raise ValueError(f"images {h} x {w}: sides of 1..{FIG_MAX_SIZE} are supported")
+    if not 1 <= b <= 65535 or images.numel() >= 2 ** 31:
+        raise ValueError(f"images: B={b} outside 1..65535, or B x 3 x H x W >= 2^31")
+    pp, pp_p = _host_table(prim_ptr, np.int32, None, "prim_ptr")
+    pr, pr_p = _host_table(np.asarray(prims, dtype=np.float32).reshape(-1, PRIM_FLOATS), np.float32, PRIM_FLOATS,
+                           "prims")
+    n = pr.shape[0]
+    if pp.size != b + 1 or pp[0] < 0 or pp[-1] > n or np.any(np.diff(pp) < 0):
+        raise ValueError(f"prim_ptr: expected {b + 1} ascending entries within [0, {n}]")
+    if n > PRIM_MAX:
+        raise ValueError(f"{n} primitives: at most {PRIM_MAX} are supported")
+    if n:
+        clip = pr[:, 12:16]
+        if np.any(clip != np.floor(clip)) or np.any(clip[:, :2] < 0) or np.any(clip[:, 2] > w) or \
+                np.any(clip[:, 3] > h) or np.any(clip[:, 2] < clip[:, 0]) or np.any(clip[:, 3] < clip[:, 1]):
+            raise ValueError(f"prims: a clip rectangle lies outside the {h} x {w} image")
+    d_pp = torch.from_numpy(pp).to(images.device)
+    d_pr = torch.from_numpy(pr).to(images.device) if n else None
+    call("cfsd_draw_primitives", ptr(images), ptr(d_pr), ptr(d_pp), pr_p if n else None, pp_p, b, h, w, n,
+         stream_ptr())
+    return images

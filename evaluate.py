@@ -15,7 +15,11 @@ classifiers and is not part of the whole run, as in the reference), plan
 moved to the healthy distribution, procedure by procedure, under
 ``interpolations/``) and prepost (``--pairs FILE --pairs-root DIR``: the
 surgical-effectiveness metrics of every pre- / post-operative pair of the
-table, under ``pre_post_eval/``); neither is part of the whole run either."""
+table, under ``pre_post_eval/``) and figures (the embedding figures drawn on
+the device, ``lda_emb_*.png`` and the region sheets, or ``tsne_emb_*.png``
+without classifiers; with ``--patient`` the path to normal on them, with
+``--pairs`` / ``--pairs-root`` the pre / post arrows, under
+``pre_post_eval_plots/``); none of these is part of the whole run either."""
 import os
 import sys
 

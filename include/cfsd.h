@@ -1169,6 +1169,98 @@ int cfsd_pair_metrics(const float* z_pre, const float* z_post, const int32_t* wi
                       const float* whiten, float* raw, int n, int latent, int n_windows, int mean_floats,
                       int whiten_floats, void* stream);
 
+/* ---------------------------------------------------------------- embedding figures
+ * The pictures of Tester.plot_embeddings / plot_embeddings_per_region
+ * (test.py:1161-1321), _render_embed_save_z_interpolations (test.py:750-833)
+ * and _project_pre_post_pair (test.py:1090-1136), ABI 4.23: the kernel density
+ * estimates seaborn's kdeplot takes from scipy's gaussian_kde, their iso-level
+ * bands shaded into an image, and point / line / arrow overlays.  No atomics;
+ * every sum and every blend runs in the order of its input, so the same input
+ * gives the same bits.  Every entry point checks its arguments, HOST tables
+ * included, before any HIP call.  The small tables (sets, panels, layers) are
+ * HOST arrays that reach the kernels by value, a few rows per launch.
+ *
+ * cfsd_kde2d: points [n_points, 2] float64; set_ptr a HOST array [n_sets + 1]
+ * int32, set s owns the points set_ptr[s] .. set_ptr[s + 1] (ascending, within
+ * [0, n_points]); params a HOST array [n_sets, 8] float64 per set: L00, L10, L11
+ * (the lower-triangular factor of the inverse kernel covariance), scale, lo0,
+ * step0, lo1, step1 (steps > 0); 2 <= G <= CFSD_KDE_MAX_G.  density [n_sets, G,
+ * G] float64:
+ *   g = (lo0 + i step0, lo1 + j step1)   (each rounded once, nothing fused)
+ *   u = L^T (g - x_k) = (L00 d0 + L10 d1, L11 d1)
+ *   density[s, i, j] = scale * sum_k exp(-(u0^2 + u1^2) / 2),  k in point order.
+ * One thread per node, the set's points staged through LDS CFSD_KDE_CHUNK at a
+ * time.  An empty set gives zeros; a set's grid does not depend on the other
+ * sets of the call.
+ *
+ * cfsd_density_shade: image [3, H, W] fp32, shaded in place; grids a device
+ * array of grid_doubles float64 holding the density grids; panels a HOST array
+ * [n_panels <= CFSD_SHADE_MAX_PANELS, CFSD_SHADE_PANEL_DOUBLES]: px0, py0, pw,
+ * ph (the pixel rectangle, whole numbers, inside the image, panels disjoint),
+ * xlo, xhi, ylo, yhi (the data window; y grows upwards, row py0 is yhi);
+ * layers a HOST array [n_layers <= CFSD_SHADE_MAX_LAYERS,
+ * CFSD_SHADE_LAYER_DOUBLES]:
+ *   0 panel   1 offset of the grid in `grids`   2, 3 its sizes G0, G1 (node (i, j)
+ *   at offset + i G1 + j)   4 lo0   5 step0   6 lo1   7 step1   8 K (1 ..
+ *   CFSD_SHADE_MAX_LEVELS)   9..16 the K ascending levels   17..20 red, green,
+ *   blue, alpha in [0, 1]   21 fill (0 / 1)   22 line (0 / 1)   23 unused.
+ * Per pixel (x, y) of a panel, in float64 with nothing fused:
+ *   tx = (x + 0.5 - px0) / pw,  dx = xlo + tx (xhi - xlo),  u = (dx - lo0) / step0
+ *   ty = (y + 0.5 - py0) / ph,  dy = yhi - ty (yhi - ylo),  v = (dy - lo1) / step1
+ *   d = 0 unless 0 <= u <= G0 - 1 and 0 <= v <= G1 - 1; else with i0 = min(floor
+ *   u, G0 - 2), fu = u - i0 (j0, fv alike):
+ *     d = (g[i0,j0] (1 - fu) + g[i0+1,j0] fu) (1 - fv) + (g[i0,j0+1] (1 - fu) + g[i0+1,j0+1] fu) fv
+ *   band b = #{k : level_k <= d}.
+ * Layers apply in order, in fp32 with nothing fused: with fill and b >= 1,
+ * t = min(b, K - 1) / (K - 1) (1 for K = 1), shade = (1 - t) + colour t, out =
+ * out (1 - alpha) + shade alpha; with line, where b differs from the band of the
+ * pixel to the right or of the pixel below (those inside the panel), out = out
+ * (1 - alpha) + colour alpha.  A pixel no layer touches is not written.
+ *
+ * cfsd_draw_primitives: images [B, 3, H, W] fp32, composited in place; prims
+ * [n_prims, CFSD_PRIM_FLOATS] fp32 and prim_ptr [B + 1] int32 on the DEVICE,
+ * prims_host / prim_ptr_host the same tables on the HOST (these are checked;
+ * the kernel clamps what it reads from the device copies).  Image b takes the
+ * primitives prim_ptr[b] .. prim_ptr[b + 1] in order.  A row: kind, x0, y0, x1,
+ * y1, x2, y2, r, red, green, blue, alpha, clip x0, y0, x1, y1 (pixels; the clip
+ * rectangle [x0, x1) x [y0, y1) in whole pixels inside the image).  Coverage at
+ * the pixel centre p = (x + 0.5, y + 0.5):
+ *   CFSD_PRIM_DISC      clamp(r + 0.5 - |p - (x0, y0)|, 0, 1)
+ *   CFSD_PRIM_SEGMENT   clamp(r + 0.5 - dist(p, segment), 0, 1), r the half-width;
+ *                       a zero-length segment is the disc of radius r
+ *   CFSD_PRIM_TRIANGLE  clamp(0.5 - max_i e_i(p), 0, 1), e_i the signed distance
+ *                       to edge i's line, positive outside for either
+ *                       orientation; nothing for a zero-area triangle
+ * and out = out (1 - alpha cov) + colour (alpha cov) in fp32 where cov > 0.
+ * One workgroup per tile of 32 x 8 pixels walks its image's primitives in
+ * rounds of CFSD_PRIM_ROUND through LDS, each culled by the bounding box of
+ * where its coverage is positive (a disc's or segment's box grown by r + 0.5;
+ * for a triangle the box of its three mitre points, a tip of interior angle t
+ * reaching 1 / (2 sin(t / 2)) past its vertex) against the tile and the clip
+ * rectangle: the result does not depend on where the tile borders fall.
+ * CFSD_EINVAL: a null pointer, G < 2, K > CFSD_SHADE_MAX_LEVELS, a decreasing
+ * set_ptr / prim_ptr, a rectangle outside the image, sizes outside the limits. */
+#define CFSD_KDE_CHUNK 512
+#define CFSD_KDE_MAX_G 4096
+#define CFSD_FIG_MAX_SIZE 8192
+#define CFSD_SHADE_MAX_PANELS 16
+#define CFSD_SHADE_MAX_LAYERS 4096
+#define CFSD_SHADE_MAX_LEVELS 8
+#define CFSD_SHADE_PANEL_DOUBLES 8
+#define CFSD_SHADE_LAYER_DOUBLES 24
+#define CFSD_PRIM_ROUND 256
+#define CFSD_PRIM_FLOATS 16
+#define CFSD_PRIM_MAX 16777216
+#define CFSD_PRIM_DISC 0
+#define CFSD_PRIM_SEGMENT 1
+#define CFSD_PRIM_TRIANGLE 2
+int cfsd_kde2d(const double* points, const int32_t* set_ptr, const double* params, double* density, int n_points,
+               int n_sets, int G, void* stream);
+int cfsd_density_shade(float* image, const double* grids, const double* panels, const double* layers, int H, int W,
+                       int n_panels, int n_layers, int grid_doubles, void* stream);
+int cfsd_draw_primitives(float* images, const float* prims, const int32_t* prim_ptr, const float* prims_host,
+                         const int32_t* prim_ptr_host, int B, int H, int W, int n_prims, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
