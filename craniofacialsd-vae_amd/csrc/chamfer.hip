@@ -27,6 +27,7 @@
 #include <math.h>
 
 #include "cfsd_common.h"
+#include "nn_dist.h"
 
 namespace cfsd {
 
@@ -57,17 +58,11 @@ static NnSplit nn_split(int batch, int n, int p) {
   return s;
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// Squared distances of the lane's two queries to one reference point.  One
-// fixed rounding sequence (mul, fma, fma) wherever a pair is evaluated -- full
-// chunk, tail loop or the closing re-scan -- so the same pair always gives the
-// same bits.  The two queries ride in the halves of packed fp32 operands.
-__device__ __forceinline__ f32x2 nn_dist(f32x2 qx, f32x2 qy, f32x2 qz, float rx, float ry, float rz) {
-#pragma clang fp contract(off)
-  const f32x2 dx = qx - (f32x2){rx, rx}, dy = qy - (f32x2){ry, ry}, dz = qz - (f32x2){rz, rz};
-  return __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
-}
+// Squared distances of the lane's two queries to one reference point: nn_dist
+// (nn_dist.h, shared with the grid search).  One fixed rounding sequence
+// (mul, fma, fma) wherever a pair is evaluated -- full chunk, tail loop or the
+// closing re-scan -- so the same pair always gives the same bits.  The two
+// queries ride in the halves of packed fp32 operands.
 
 // Block (b, s, qb): queries [qb * kNnQpb, +kNnQpb) of batch b against the
 // reference points [s * seg_len, min(p, (s + 1) * seg_len)) of batch b (or of

@@ -1422,7 +1422,7 @@ __global__ void step_begin_k(int* __restrict__ counter, unsigned long long seed,
 
 using namespace cfsd;
 
-extern "C" int cfsd_version(void) { return (4 << 16) | 23; }  // 4.23: cfsd_kde2d, cfsd_density_shade, cfsd_draw_primitives (embedding figures, figures.hip); 4.22: cfsd_plan_targets, cfsd_plan_tables, cfsd_pair_metrics (surgical planning, planning.hip); 4.21: cfsd_knn_rows, cfsd_tsne_affinities, cfsd_tsne_forces, cfsd_tsne_update (t-SNE, tsne.hip); 4.20: cfsd_spiral_conv_bwd_weight_x_slabs (the code a deferred _bwd_weight_x leaves); 4.19: cfsd_spiral_conv_gen_fwd / _bwd_data / _bwd_weight / _dw_reduce, cfsd_spiral_conv_has_shape (general-shape SpiralConv); 4.18: cfsd_mlp_head_step (the classifier inside the VAE step); 4.17: cfsd_group_vertex_errors, cfsd_region_means (evaluation); 4.16: cfsd_class_stats, cfsd_discriminant_scores, cfsd_mlp_fwd, cfsd_mlp_train_steps (classifiers); 4.15: cfsd_raster_workspace, cfsd_vertex_normals, cfsd_render_vertices, cfsd_rasterize, cfsd_interpolate_colors (rendering); 4.14: cfsd_point_face, cfsd_point_face_bwd (surface fitting); 4.13: cfsd_nn_points, cfsd_chamfer_bwd (latent fitting); 4.12: cfsd_bottleneck_bwd exchange workspace + sticky error word; 4.11: cfsd_spiral_conv_bwd_flat_pair_bf16, cfsd_spiral_conv_bwd_rowsub_pair_bf16; 4.10: cfsd_spiral_conv_bwd_flat_pair; 4.9: cfsd_spiral_conv_fwd_in_swap; 4.8: cfsd_bottleneck_bwd; 4.7: cfsd_adam_scaled; 4.6: cfsd_side_work (side work riding in host launches); 3.0: per-epoch shuffle, bf16 path; 3.1: row-subset backward; 3.2: uniform / visiting-order SpMM; 3.3: reduce + Adam; 4.0: CFSD_VM vertex-major operands (dx_dt / dpre_dt arguments); 4.1: fp32 vertex-major operands; 4.2: vertex-major swap / loss passes (_x); 4.3: cfsd_dw_slabs.fused == 3 (vertex-major fp32 dW slabs); 4.4: cfsd_gather_meshes
+extern "C" int cfsd_version(void) { return (4 << 16) | 24; }  // 4.24: cfsd_nn_grid_build, cfsd_nn_points_grid (exact uniform-grid nearest neighbour, nn_grid.hip); 4.23: cfsd_kde2d, cfsd_density_shade, cfsd_draw_primitives (embedding figures, figures.hip); 4.22: cfsd_plan_targets, cfsd_plan_tables, cfsd_pair_metrics (surgical planning, planning.hip); 4.21: cfsd_knn_rows, cfsd_tsne_affinities, cfsd_tsne_forces, cfsd_tsne_update (t-SNE, tsne.hip); 4.20: cfsd_spiral_conv_bwd_weight_x_slabs (the code a deferred _bwd_weight_x leaves); 4.19: cfsd_spiral_conv_gen_fwd / _bwd_data / _bwd_weight / _dw_reduce, cfsd_spiral_conv_has_shape (general-shape SpiralConv); 4.18: cfsd_mlp_head_step (the classifier inside the VAE step); 4.17: cfsd_group_vertex_errors, cfsd_region_means (evaluation); 4.16: cfsd_class_stats, cfsd_discriminant_scores, cfsd_mlp_fwd, cfsd_mlp_train_steps (classifiers); 4.15: cfsd_raster_workspace, cfsd_vertex_normals, cfsd_render_vertices, cfsd_rasterize, cfsd_interpolate_colors (rendering); 4.14: cfsd_point_face, cfsd_point_face_bwd (surface fitting); 4.13: cfsd_nn_points, cfsd_chamfer_bwd (latent fitting); 4.12: cfsd_bottleneck_bwd exchange workspace + sticky error word; 4.11: cfsd_spiral_conv_bwd_flat_pair_bf16, cfsd_spiral_conv_bwd_rowsub_pair_bf16; 4.10: cfsd_spiral_conv_bwd_flat_pair; 4.9: cfsd_spiral_conv_fwd_in_swap; 4.8: cfsd_bottleneck_bwd; 4.7: cfsd_adam_scaled; 4.6: cfsd_side_work (side work riding in host launches); 3.0: per-epoch shuffle, bf16 path; 3.1: row-subset backward; 3.2: uniform / visiting-order SpMM; 3.3: reduce + Adam; 4.0: CFSD_VM vertex-major operands (dx_dt / dpre_dt arguments); 4.1: fp32 vertex-major operands; 4.2: vertex-major swap / loss passes (_x); 4.3: cfsd_dw_slabs.fused == 3 (vertex-major fp32 dW slabs); 4.4: cfsd_gather_meshes
 extern "C" const char* cfsd_last_error_string(void) { return g_err; }
 
 extern "C" int cfsd_recon_lap_blocks(int batch, int nv) {

@@ -12,7 +12,9 @@ landmarks on it, find the latent code whose decoded head matches the scan:
    search; pytorch3d has no ROCm build) or, when the scan's and the
    template's faces are given, :func:`ops.surface_distance` (HIP
    point-to-triangle search: the distance to the SURFACES, free of the
-   vertex-to-vertex term's sampling floor); the decoder runs through
+   vertex-to-vertex term's sampling floor); ``search="grid"`` finds the
+   Chamfer term's neighbours through exact uniform grids, for dense raw
+   scans (bit-identical results); the decoder runs through
    ``model.py``'s autograd Functions with its parameters frozen, which
    selects their data-gradient-only backward;
 3. :func:`fit_main` -- the ``fit.py`` command line.
@@ -109,7 +111,7 @@ def frozen(module):
 
 def fit_points(decode, target_points, target_landmarks, landmark_idx, mean, std, latent_mean, latent_std=None,
                n_starts=16, lr=5e-3, iterations=250, seed=0, selection_weights=(10.0, 1.0), landmark_weight=10.0,
-               module=None, target_faces=None, template_faces=None):
+               module=None, target_faces=None, template_faces=None, search="brute"):
     """The optimisation loop of ``Tester.fit_mesh`` (``test.py:381-443``).
 
     ``decode(z [n_starts, latent]) -> [n_starts, V, 3]`` with autograd (e.g.
@@ -140,6 +142,14 @@ def fit_points(decode, target_points, target_landmarks, landmark_idx, mean, std,
     target_faces)`` in the loss, in ``errors_shape`` and in the history, and
     fill ``surface_mm``; without them the loop is the vertex path unchanged.
 
+    ``search``: how the Chamfer term finds its nearest neighbours.
+    ``"brute"`` (the default) walks every pair; ``"grid"`` -- for DENSE raw
+    scans, a few hundred thousand points and more -- searches uniform grids
+    (``ops.PointGrid``): the grid over the scan is built once before the loop,
+    the grids over the decoded heads every iteration, and every result is bit
+    for bit that of ``"brute"``.  The surface term has its own culled search:
+    ``search="grid"`` together with faces raises ``ValueError``.
+
     The best start is the argmin of ``w0 * errors_lnd + w1 * errors_shape``
     with ``selection_weights = (w0, w1)``.  The reference (``test.py:442``)
     computes ``10 * errors_lnd + errors_lnd``: the landmark error twice and
@@ -155,6 +165,10 @@ def fit_points(decode, target_points, target_landmarks, landmark_idx, mean, std,
         module = decode.__self__
     if (target_faces is None) != (template_faces is None):
         raise ValueError("fit_points: target_faces and template_faces go together")
+    if search not in ("brute", "grid"):
+        raise ValueError(f'fit_points: search={search!r}, expected "brute" or "grid"')
+    if search == "grid" and target_faces is not None:
+        raise ValueError('fit_points: search="grid" is the vertex path\'s; the surface term (faces) has its own search')
     dev = target_points.device
     target = target_points.detach().to(torch.float32).reshape(1, -1, 3).contiguous()
     lnd = target_landmarks.detach().to(dev, torch.float32).reshape(1, -1, 3)
@@ -176,10 +190,12 @@ def fit_points(decode, target_points, target_landmarks, landmark_idx, mean, std,
     lnd_hist = torch.zeros(iterations, dtype=torch.float32, device=dev)
     verts = None
     scan = None if target_faces is None else ops.SurfaceMesh(target, target_faces)
+    if search == "grid":
+        target = ops.PointGrid(target)  # built once: the scan is constant
 
     def shape_term(v, batch_reduction="mean"):
         if scan is None:
-            return ops.chamfer_distance(v, target, batch_reduction=batch_reduction)[0]
+            return ops.chamfer_distance(v, target, batch_reduction=batch_reduction, search=search)[0]
         return ops.surface_distance(v, template_faces, scan, batch_reduction=batch_reduction)
 
     surface_mm = None
@@ -242,9 +258,14 @@ def fit_main(argv=None):
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--surface", action="store_true",
                         help="fit to the scan's triangles (its f lines), not its vertices")
+    parser.add_argument("--search", choices=("brute", "grid"), default="brute",
+                        help="nearest-neighbour search of the Chamfer term: grid is for dense raw scans "
+                             "(same result, bit for bit); not with --surface")
     parser.add_argument("--classifiers", default=None, metavar="CHECKPOINT_DIR",
                         help="folder holding the classifier files of train.py: also report the fit's class")
     opts = parser.parse_args(argv)
+    if opts.surface and opts.search != "brute":
+        parser.error("--search grid is the vertex path's; --surface has its own culled search")
 
     from . import data as D
     from . import manager as M
@@ -268,7 +289,8 @@ def fit_main(argv=None):
             raise ValueError(f"--surface: {opts.mesh} has no faces")
     res, aligned = manager.fit_mesh(scan, read_landmarks(opts.landmarks), landmark_idx,
                                     norm, torch.load(opts.z_stats, weights_only=True), faces=faces, lr=opts.lr,
-                                    iterations=opts.iterations, n_starts=opts.n_starts, seed=opts.seed)
+                                    iterations=opts.iterations, n_starts=opts.n_starts, seed=opts.seed,
+                                    search=opts.search)
     D.write_obj(opts.out + "_fit.obj", res.verts.cpu().numpy(), manager.template.faces)
     D.write_obj(opts.out + "_aligned.obj", aligned, faces)
     shape_key = "surface_term_mm" if opts.surface else "chamfer_mm"

@@ -352,7 +352,10 @@ class ModelManager(ClassifierStage):
         (``**kw``: its options).  ``faces`` ``[Fs, 3]`` (the scan's triangles,
         zero-based) switches the shape term to the distance between the
         SURFACES of the scan and of the decoded heads (the template's faces)
-        and fills ``surface_mm``.  Returns ``(FitResult, aligned_verts)``;
+        and fills ``surface_mm``.  ``search="grid"`` (one of the options)
+        searches the vertex path's nearest neighbours through uniform grids,
+        for dense raw scans: the same result, bit for bit.  Returns
+        ``(FitResult, aligned_verts)``;
         the result's errors, histories and ``surface_mm`` are multiplied by
         ``to_mm_const``."""
         from . import fitting

@@ -1324,11 +1324,120 @@ def chamfer_bwd(x, y, idx_xy, idx_yx, wx, wy):
     return gx
 
 
+NN_GRID_MAX = _H["CFSD_NN_GRID_MAX"]  # most cells per axis of a PointGrid
+# Points per cell the default cell count aims at, counted as P / g^2: the point sets of a fit are SURFACES, which
+# occupy about g^2 of the g^3 cells.  Chosen by the sweep of tools/bench_fit_grid.py (profiles/fit_grid_sweep.json,
+# DESIGN 8.2): the fastest of 1, 2, 4, 8, 16, 32 at every scan size.
+NN_GRID_POINTS_PER_CELL = 32.0
+
+
+def default_grid_cells(p):
+    """The ``cells=None`` rule of :class:`PointGrid`: ``(g, g, g)`` with ``g =
+    round(sqrt(P / NN_GRID_POINTS_PER_CELL))`` held to ``1 .. NN_GRID_MAX`` -- a
+    function of the point COUNT alone, so choosing it reads nothing back."""
+    g = int(min(max(round((int(p) / NN_GRID_POINTS_PER_CELL) ** 0.5), 1), NN_GRID_MAX))
+    return (g, g, g)
+
+
+def _grid_cells(cells, p):
+    if cells is None:
+        return default_grid_cells(p)
+    try:
+        cells = tuple(cells)
+        ok = len(cells) == 3 and all(isinstance(g, int) and not isinstance(g, bool) for g in cells)
+    except TypeError:
+        ok = False
+    if not ok or not all(1 <= g <= NN_GRID_MAX for g in cells):
+        raise ValueError(f"PointGrid: cells={cells!r}, expected None or three integers in 1..{NN_GRID_MAX}")
+    return cells
+
+
+class PointGrid:
+    """A point set ``[B, P, 3]`` (or ``[P, 3]``) with its uniform grid
+    (``cfsd_nn_grid_build``) as the reference side of :func:`nn_points_grid`: a
+    CONSTANT set is built once and searched many times, as
+    :class:`SurfaceMesh` is for the surface term.  ``cells`` ``(gx, gy, gz)``,
+    each in ``1 .. NN_GRID_MAX``, or None for :func:`default_grid_cells`.
+    Every batch element has its own grid over its own bounding box; the box
+    is computed on the device and never read back.
+
+    A single set (``B = 1``) also holds ``queries`` ``[1, P, 3]``, its points
+    in Morton order, and ``perm`` (``queries[0, i] = points[0, perm[i]]``),
+    for searches FROM the set: a wave's 64 queries should be neighbours in
+    space and a scan's vertex order is arbitrary (``queries=False`` skips
+    them)."""
+
+    def __init__(self, points, cells=None, queries=True):
+        if not isinstance(points, torch.Tensor):
+            raise ValueError("PointGrid: points must be a device float32 tensor [B, P, 3] or [P, 3]")
+        cells = _grid_cells(cells, points.shape[-2] if points.dim() >= 2 else 1)
+        points = points.detach()
+        if points.dim() == 2:
+            points = points[None]
+        points = points.contiguous()
+        self.batch, self.p = _points(points, "points")
+        self.points, self.cells = points, cells
+        gx, gy, gz = cells
+        need = int(_abi.lib().cfsd_nn_grid_build_workspace(self.batch, self.p, gx, gy, gz))
+        if need <= 0:
+            raise ValueError(f"PointGrid: {self.batch} x {self.p} points in {cells} cells exceed 32-bit indices")
+        self.workspace = torch.empty(need // 4, dtype=torch.int32, device=points.device)
+        self.nbytes = ctypes.c_size_t(need)
+        n = self.batch * self.p
+        ids = self.workspace[need // 4 - (n + 3) // 4 * 4:][:n].view(self.batch, self.p)  # the buffer's last section
+        self._build(_H["CFSD_NN_GRID_CELLS"], None, None)
+        keys, order = torch.sort(ids, dim=1, stable=True)
+        self._build(_H["CFSD_NN_GRID_GROUP"], keys.contiguous(), order.contiguous())
+        self.queries = self.perm = None
+        if queries and self.batch == 1:
+            order = _morton_order(points[0])
+            self.queries = points.index_select(1, order).contiguous()
+            self.perm = order.to(torch.int32)
+
+    def _build(self, stage, keys, order):
+        gx, gy, gz = self.cells
+        call("cfsd_nn_grid_build", ptr(self.points), ptr(self.workspace), self.nbytes, stage, ptr(keys), ptr(order),
+             self.batch, self.p, gx, gy, gz, stream_ptr())
+
+
+def nn_points_grid(q, grid, return_stats=False):
+    """:func:`nn_points` through a uniform grid (``cfsd_nn_points_grid``):
+    ``q`` ``[Bq, N, 3]`` against ``grid``, a :class:`PointGrid` over ``[Br, P,
+    3]``; ``Bq`` and ``Br`` equal or 1.  Exact: ``(dist2, idx)`` are bit for
+    bit those of ``nn_points(q, grid.points)``, equal distances resolved to
+    the lowest index, in the caller's order.  ``q`` may itself be a single-set
+    :class:`PointGrid`: its points then query in Morton order and the results
+    are written back in the set's own order.  ``return_stats`` appends the
+    int32 ``[B, N]`` count of points evaluated per query."""
+    if not isinstance(grid, PointGrid):
+        raise ValueError("nn_points_grid: grid must be a PointGrid")
+    perm = None
+    if isinstance(q, PointGrid):
+        q, perm = (q.queries, q.perm) if q.perm is not None else (q.points, None)
+    if not isinstance(q, torch.Tensor) or q.dim() != 3:
+        raise ValueError("nn_points_grid: q must be a [B, N, 3] tensor or a PointGrid")
+    bsz = _pair_batch(int(q.shape[0]), grid.batch, "nn_points_grid")
+    bq, n = _points(q, "q")
+    if grid.points.device != q.device:
+        raise ValueError("q and the grid must be on one device")
+    dist2 = torch.empty((bsz, n), dtype=torch.float32, device=q.device)
+    idx = torch.empty((bsz, n), dtype=torch.int32, device=q.device)
+    count = torch.empty((bsz, n), dtype=torch.int32, device=q.device) if return_stats else None
+    gx, gy, gz = grid.cells
+    call("cfsd_nn_points_grid", ptr(q), ptr(grid.workspace), grid.nbytes, ptr(perm), ptr(dist2), ptr(idx), ptr(count),
+         bsz, bq, grid.batch, n, grid.p, gx, gy, gz, stream_ptr())
+    return (dist2, idx, count) if return_stats else (dist2, idx)
+
+
 class _ChamferFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, y, point_mean):
-        d_xy, i_xy = nn_points(x, y)
-        d_yx, i_yx = nn_points(y, x)
+    def forward(ctx, x, y, point_mean, y_grid=None):
+        if y_grid is None:
+            d_xy, i_xy = nn_points(x, y)
+            d_yx, i_yx = nn_points(y, x)
+        else:  # the same distances and indices, bit for bit, through the grids
+            d_xy, i_xy = nn_points_grid(x, y_grid)
+            d_yx, i_yx = nn_points_grid(y_grid if y_grid.perm is not None else y, PointGrid(x, queries=False))
         ctx.save_for_backward(x, y, i_xy, i_yx)
         ctx.point_mean = point_mean
         cx, cy = d_xy.sum(1), d_yx.sum(1)
@@ -1342,11 +1451,11 @@ class _ChamferFn(torch.autograd.Function):
         g = g.contiguous().to(torch.float32)
         wx = g / x.shape[1] if ctx.point_mean else g
         wy = g / y.shape[1] if ctx.point_mean else g.clone()
-        return chamfer_bwd(x, y, i_xy, i_yx, wx.contiguous(), wy.contiguous()), None, None
+        return chamfer_bwd(x, y, i_xy, i_yx, wx.contiguous(), wy.contiguous()), None, None, None
 
 
 def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None,
-                     batch_reduction="mean", point_reduction="mean", norm=2):
+                     batch_reduction="mean", point_reduction="mean", norm=2, search="brute"):
     """The subset of ``pytorch3d.loss.chamfer_distance`` the reference's
     fitting uses (``test.py:404-405, 427-429``), on libcfsd.
 
@@ -1356,7 +1465,22 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_nor
     ``y`` to ``x``; then ``batch_reduction`` ``"mean"``, ``"sum"`` or ``None``
     (``[B]``).  Lengths, normals, weights and other norms raise
     ``ValueError``.  Returns ``(loss, None)`` like pytorch3d (no normals
-    term)."""
+    term).
+
+    ``search``: ``"brute"`` (the default) walks every pair (``nn_points``);
+    ``"grid"`` runs both directions through uniform grids
+    (:func:`nn_points_grid`) -- for dense targets.  ``y`` may then be a
+    :class:`PointGrid`, built once and reused over many calls; the grid over
+    ``x`` is built per call.  Loss and gradient are bit-identical to
+    ``"brute"``: the same distances summed in the same order, the same indices
+    into the same ``chamfer_bwd``.  Any other value raises ``ValueError``."""
+    if search not in ("brute", "grid"):
+        raise ValueError(f'chamfer_distance: search={search!r}, expected "brute" or "grid"')
+    y_grid = None
+    if isinstance(y, PointGrid):
+        if search != "grid":
+            raise ValueError('chamfer_distance: a PointGrid target needs search="grid"')
+        y_grid, y = y, y.points
     if x_lengths is not None or y_lengths is not None:
         raise ValueError("chamfer_distance: x_lengths / y_lengths are not supported (dense point sets only)")
     if x_normals is not None or y_normals is not None:
@@ -1376,7 +1500,9 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_nor
     by, _ = _points(y, "y")
     if by not in (1, bsz):
         raise ValueError(f"chamfer_distance: y batch {by} must be 1 or {bsz}")
-    per_batch = _ChamferFn.apply(x, y, point_reduction == "mean")
+    if search == "grid" and y_grid is None:
+        y_grid = PointGrid(y)
+    per_batch = _ChamferFn.apply(x, y, point_reduction == "mean", y_grid)
     if batch_reduction == "mean":
         return per_batch.sum() / bsz, None
     if batch_reduction == "sum":

@@ -1,9 +1,11 @@
 """``python fit.py --config C --checkpoint-dir D --mesh scan.obj --landmarks
 lm.json --template-landmarks idx.json --z-stats z_stats.pt --out PREFIX
-[--surface]``: fit a trained model to an unregistered scan (the reference's
+[--surface] [--search {brute,grid}]``: fit a trained model to an unregistered scan (the reference's
 Tester.fit_mesh, test.py:336-520) on the MI355X path
 (craniofacialsd-vae_amd/fitting.py); ``--surface`` fits to the scan's
 triangles instead of its vertices and reports the surface error;
+``--search grid`` finds the Chamfer term's nearest neighbours through uniform
+grids (dense raw scans; the same result as ``brute``, bit for bit);
 ``--classifiers CHECKPOINT_DIR`` also reports the fit's QDA class and its
 Mahalanobis distance to the normal class."""
 import os

@@ -775,6 +775,55 @@ int cfsd_chamfer_bwd(const float* x, const float* y, const int32_t* idx_xy, cons
                      const int32_t* seg_j, const float* wx, const float* wy, float* gx, int batch, int by,
                      int n, int p, void* stream);
 
+/* Exact nearest neighbour over a uniform grid, for dense point sets (ABI 4.24,
+ * nn_grid.hip): the result of cfsd_nn_points BIT FOR BIT -- the same distance
+ * (one shared instruction sequence, nn_dist.h) and the same index, bit-equal
+ * distances resolved to the lowest original index -- at a cost that follows
+ * the points near a query, not all of them.
+ *
+ * cfsd_nn_grid_build: r [br, p, 3] fp32, gx x gy x gz cells (each 1 ..
+ * CFSD_NN_GRID_MAX) over the bounding box of EACH batch element, computed on
+ * the device and never read back.  An axis whose extent is zero (planar,
+ * collinear, coincident or single points) or not finite puts every point in
+ * cell 0 of that axis.  `grid` is a 16-byte aligned device buffer of
+ * cfsd_nn_grid_build_workspace() bytes (0 = bad sizes), laid out as
+ *   records    [br, p] x 16 bytes: x, y, z and the original index (int32 bits),
+ *              grouped by cell, cell id = (cz gy + cy) gx + cx ascending;
+ *   header     [br, CFSD_NN_GRID_HDR] floats: lo, cell size, inverse cell
+ *              size, extent, each as x y z 0;
+ *   cell_start [br, gx gy gz + 1] int32 (padded to 16 bytes): the records of
+ *              cell c are [cell_start[c], cell_start[c + 1]);
+ *   cell_id    [br, p] int32 (padded to 16 bytes): every point's cell.
+ * Two stages with the caller's sort between them (the project's usual
+ * grouping, as for cfsd_chamfer_bwd):
+ *   CFSD_NN_GRID_CELLS  writes header and cell_id (sorted_ids, order: NULL);
+ *   CFSD_NN_GRID_GROUP  takes sorted_ids [br, p] int32, the ids of each batch
+ *                       element ascending, and order [br, p] int64, the point
+ *                       at each sorted position, and writes cell_start and
+ *                       the records.  The order inside a cell is free: query
+ *                       results do not depend on it.
+ * No atomics.
+ *
+ * cfsd_nn_points_grid: q [bq, n, 3] against a built grid of br sets; bq and
+ * br each 1 or `batch`, as for cfsd_nn_points.  One lane per query walks the
+ * cells around its own in shells of growing Chebyshev radius and stops only
+ * when its best distance is STRICTLY below a lower bound (shrunk by a derived
+ * rounding margin, nn_grid.hip) of everything not yet visited; at most
+ * max(gx, gy, gz) shells, for any input.  dist2, idx [batch, n] as
+ * cfsd_nn_points.  q_perm [n] int32 or NULL: query i writes position
+ * q_perm[i] of its row (queries given in a space-filling order, results in the
+ * caller's).  count [batch, n] int32 or NULL: the points evaluated per query. */
+#define CFSD_NN_GRID_MAX 128
+#define CFSD_NN_GRID_HDR 16
+#define CFSD_NN_GRID_CELLS 0
+#define CFSD_NN_GRID_GROUP 1
+size_t cfsd_nn_grid_build_workspace(int br, int p, int gx, int gy, int gz);
+int cfsd_nn_grid_build(const float* r, void* grid, size_t grid_bytes, int stage, const int32_t* sorted_ids,
+                       const int64_t* order, int br, int p, int gx, int gy, int gz, void* stream);
+int cfsd_nn_points_grid(const float* q, const void* grid, size_t grid_bytes, const int32_t* q_perm, float* dist2,
+                        int32_t* idx, int32_t* count, int batch, int bq, int br, int n, int p, int gx, int gy, int gz,
+                        void* stream);
+
 /* ---------------------------------------------------------------- surface fitting
  * Distance of points to a triangle mesh (Tester._point_mesh_distance,
  * test.py:522-533: pytorch3d's point_face_distance), ABI 4.14.
